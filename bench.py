@@ -7,15 +7,20 @@ lambda = 3.0) + ``_latents_to_images`` (VAE decode) + the uint8 pack of the fram
 RCCL all-gather of the decoded (uint8) frames.  Workload = BASELINE.json configs[1] per rank (weak scaling: 4 images per GPU).
 Weights are seeded random tensors of the SD-1.4 / DADD architecture (no checkpoints offline).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      (no torchrun environment: starts that same command itself, as a child process)
 
-Rank 0 prints ONE JSON line.  ``roofline`` is measured live: after the timed region the same UNet
-step is launched eagerly with every implicit-GEMM launch bracketed by HIP events on its own stream
-(graph replays cannot carry per-kernel events); ``cpu_baseline`` times the CPU oracle (a port of the
-reference's CPU path) on a bounded sample on rank 0 at N = 1.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the ``--steps`` passes and prints
+it (``ms_per_step`` = wall time of one timed pass).  ``--dump-outputs DIR`` then writes what the last
+timed pass computed as float32 ``.npy`` files: ``frames`` (the gathered uint8 NHWC frames, as values
+0..255) and ``latents`` (rank 0's final DDIM latents); inputs and weights are seeded, so two builds
+can be compared file by file.  ``--full`` adds the measurements that take runs of their own:
+``roofline``, measured live (after the timed region the same UNet step is launched eagerly with every
+implicit-GEMM launch bracketed by HIP events on its own stream; graph replays cannot carry per-kernel
+events), and ``cpu_baseline``, which times the CPU oracle (a port of the reference's CPU path) on a
+bounded sample on rank 0 at N = 1.
 """
 from __future__ import annotations
 
@@ -25,6 +30,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -43,8 +49,12 @@ def parse():
     p.add_argument("--batch", type=int, default=4)
     p.add_argument("--ddim-steps", type=int, default=50)
     p.add_argument("--steer-scale", type=float, default=3.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the live roofline of the dominant kernel and the CPU-oracle baseline (minutes)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the live roofline")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     p.add_argument("--tiny-clip", action="store_true", help="2-layer CLIP tower (debug only)")
     p.add_argument("--launch-selftest", action="store_true",
                    help="ranks only rendezvous (gloo without a GPU), gather one tensor and print a JSON line: the "
@@ -183,6 +193,23 @@ def live_roofline(mod, a, side, lat, dev, n_steps=2):
                              "gbs": round(t["gbs"], 1)} for t in rows[:10]]}
 
 
+DUMP_BYTES = 60 << 20             # all --dump-outputs files together stay under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """``name -> tensor`` as ``out_dir/<name>.npy`` in float32.  An array larger than its even share of ``budget``
+    (8 GPUs' gathered frames) is written as a fixed sample instead: the elements at sorted flat indices drawn with
+    seed 0, the same for every build at the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // (4 * len(arrays))
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        if x.size > share:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+
+
 def launcher_argv(n_gpus: int, argv, port: int):
     """The command the driver itself uses for N > 1 (one rank per GPU, RCCL rendezvous on 127.0.0.1)."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n_gpus}",
@@ -272,8 +299,9 @@ def main():
             z = PIPE._ddim_sample_ip(mod, target, source, pix, a.ddim_steps, dev,
                                      steer_scale=a.steer_scale, latents=lat)
             frames = PIPE._latents_to_images(mod, z)
-            return D.all_gather_frames_u8(mod.be, frames)      # uint8 NHWC frames: what the writers consume
+            return z, D.all_gather_frames_u8(mod.be, frames)      # uint8 NHWC frames: what the writers consume
 
+    t_setup = time.perf_counter()
     for _ in range(a.warmup):
         one_pass()
     torch.cuda.synchronize(dev)
@@ -283,15 +311,17 @@ def main():
     t_queue = 0.0
     for _ in range(a.steps):
         tq = time.perf_counter()
-        frames = one_pass()
+        z, frames = one_pass()
         t_queue += time.perf_counter() - tq       # host time to QUEUE a pass (no wait for the GPU inside a pass)
     torch.cuda.synchronize(dev)
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
     assert frames.shape == (n_total, a.image_size, a.image_size, 3) and frames.dtype == torch.uint8
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"frames": frames, "latents": z})
 
     roof = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         roof = live_roofline(mod, a, side, lat, dev)
 
     if rank == 0:
@@ -301,6 +331,7 @@ def main():
             "metric": "images/sec at 512x512, 50 DDIM steps, bs/GPU=4", "value": value, "unit": "images/sec",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
             "host_queue_ms_per_step": t_queue / a.steps * 1e3,
+            "setup_s": t_setup - T_START, "warmup_s": t0 - t_setup,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16",
             "data": "synthetic (seeded random-init SD-1.4/DADD weights, CPU-seeded noise, random structure image)",
             "config": {"workload": f"{a.image_size}x{a.image_size}, {a.ddim_steps} DDIM steps, bs={a.batch}/GPU, "
@@ -313,7 +344,7 @@ def main():
             if a.image_size == 512 else None,
             "roofline": roof,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, a.image_size)
         print(json.dumps(out), flush=True)
     D.barrier()

@@ -40,9 +40,9 @@ for s in $steps; do
     opbench) TAILN=80 run opbench 600 python scripts/op_bench.py "$tag" ;;
     opbenchvae) TAILN=60 run opbenchvae 600 python scripts/op_bench.py "$tag" --vae ;;
     breakdown) TAILN=20 run breakdown 600 python scripts/pass_breakdown.py ;;
-    bench)   run bench 900 python bench.py --steps 3 --warmup 1 ;;
+    bench)   run bench 900 python bench.py --steps 3 --warmup 1 --full ;;
     prof)    export TMPDIR=/tmp
-             run prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+             run prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline
              find "$out/prof" -name "*kernel_stats*.csv" | head -1 | xargs -r -I{} sh -c 'head -40 "{}" > '"$out"'/kernel_stats_top.csv'
              python scripts/trace_gaps.py "$out/prof" > "$out/trace_gaps.txt" 2>&1; tail -n 45 "$out/trace_gaps.txt"
              find "$out/prof" -name "*kernel_trace*.csv" -size +20M -delete 2>/dev/null ;;

@@ -93,3 +93,28 @@ def test_bench_launches_its_own_ranks():
     assert len(lines) == 1
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["ranks_seen"] == [0.0, 1.0] and rec["max_over_ranks"] == 1.0
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """``--dump-outputs``: float32 ``.npy`` per output, an array over its share of the budget replaced by the same
+    seeded sample on every call; ``--full`` is off unless asked for."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    frames = torch.arange(4 * 8 * 8 * 3, dtype=torch.uint8).reshape(4, 8, 8, 3)
+    latents = torch.randn(4, 4, 2, 2, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "a"), {"frames": frames, "latents": latents})
+    f, z = np.load(tmp_path / "a" / "frames.npy"), np.load(tmp_path / "a" / "latents.npy")
+    assert f.dtype == z.dtype == np.float32 and f.shape == (4, 8, 8, 3)
+    assert np.array_equal(f, frames.float().numpy()) and np.array_equal(z, latents.numpy())
+    for d in ("b", "c"):                                       # 2 arrays x 100 float32 elements each
+        bench.dump_outputs(str(tmp_path / d), {"frames": frames, "latents": latents}, budget=800)
+    fb, fc = np.load(tmp_path / "b" / "frames.npy"), np.load(tmp_path / "c" / "frames.npy")
+    idx = np.sort(np.random.default_rng(0).choice(f.size, 100, replace=False))
+    assert fb.shape == (100,) and np.array_equal(fb, fc) and np.array_equal(fb, f.reshape(-1)[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "latents.npy"), z)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None

@@ -263,7 +263,7 @@ def test_diffusers_layout_files_merge(full_sd, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------- config
-def test_load_config_yaml_with_train_ip_schema(tmp_path):
+def test_load_config_yaml_with_train_ip_schema(tmp_path, golden_dir):
     """A YAML with the reference's ``configs/train_ip.yaml`` schema -> attribute access + ``diff_cfg_from``."""
     doc = _plain(default_config())
     doc["hydra"] = {"output_subdir": None}
@@ -279,12 +279,10 @@ def test_load_config_yaml_with_train_ip_schema(tmp_path):
     assert dc.image_encoder_path == "openai/clip-vit-large-patch14" and dc.use_image_projection_plus is True
     with pytest.raises(FileNotFoundError):
         CFG.load_config(tmp_path / "nope.yaml")
-    ref_yaml = "/root/reference/configs/train_ip.yaml"      # present in the build container only
-    if os.path.exists(ref_yaml):
-        rc = CFG.load_config(ref_yaml)
-        rdc = diff_cfg_from(rc)
-        assert rdc == diff_cfg_from(default_config()), "DEFAULTS drifted from the shipped train_ip.yaml"
-        assert rc.dataset.image_size == 256 and rc.training.gradient_clip_val == 1.0
+    rc = CFG.load_config(os.path.join(golden_dir, "train_ip.yaml"))    # the reference's configs/train_ip.yaml, verbatim
+    rdc = diff_cfg_from(rc)
+    assert rdc == diff_cfg_from(default_config()), "DEFAULTS drifted from the shipped train_ip.yaml"
+    assert rc.dataset.image_size == 256 and rc.training.gradient_clip_val == 1.0
 
 
 # ------------------------------------------------------------------------------------------- images
