@@ -313,6 +313,32 @@ int dadd_purifier_tail_f16(const void* img, const void* dis, const void* gate, c
 int dadd_prefetch(const void* ptr, int64_t bytes, void* stream);
 int dadd_prefetch_join(void* stream);
 
+/* ---- bf16 operand mode of the UNet -----------------------------------------------------------
+ * The same contracts as the _f16 entry points of the same name, with every 16-bit operand and result in bf16
+ * (round to nearest even; fp32 accumulation and statistics).  Same descriptors, flags and alignment rules; the
+ * kernels behind them are the fp16 kernels compiled for bf16 storage (the csrc _bf16.hip twins).  dadd_attn_bf16 /
+ * dadd_self_attn_bf16 take d in {40, 80, 160} only; any other head dim returns DADD_EINVAL.  There is no bf16 form of
+ * the row-block fusions (attn2_fused, ffn_block, tf_head), of the VAE / conditioning entry points or of conv_cin8. */
+int dadd_conv_igemm_bf16(const dadd_igemm_desc* d, void* stream);
+int dadd_conv_in_nchw_bf16(const float* x_nchw, const void* w, const float* bias, void* out, int B, int C,
+                           int H, int W, int Cout, float* gn_ws, int gn_nchunk, void* stream);
+int dadd_conv3x3_cout4_bf16(const void* x, const void* w, const float* bias, float* out_nchw, int B,
+                            int H, int W, int C, int Cout, int mode, void* stream);
+int dadd_conv_out_ddim_bf16(const void* x, const void* w, const float* bias, float* latents, const float* coef,
+                            int B, int H, int W, int C, int Cout, void* stream);
+int dadd_groupnorm_bf16(const void* x1, int C1, const void* x2, int C2, const float* gamma,
+                        const float* beta, void* out, float* ws, int B, int HW, int groups,
+                        float eps, int silu, int ws_chunks, void* stream);
+int dadd_layernorm_bf16(const void* x, const float* gamma, const float* beta, void* out, int M,
+                        int C, float eps, void* stream);
+int dadd_self_attn_bf16(const void* q, const void* k, const void* v, void* out, int B, int N,
+                        int heads, int d, int ld_qkv, int ld_out, void* stream);
+int dadd_attn_bf16(const void* q, const void* k, const void* v, void* out, int B, int Nq, int Nk, int heads,
+                   int d, int ld_q, int ld_kv, int ld_out, void* stream);
+int dadd_tri_xattn_bf16(const void* q, const void* kv, void* out, const float* gates, float lambda,
+                        const float* lambda_dev, int mode, int B, int N, int heads, int d, int T, int ld_kv,
+                        void* stream);
+
 /* ---- hipGraph capture of the step loop ----------------------------------------------------- */
 int dadd_graph_begin(void* stream);
 int dadd_graph_end(void* stream, void** graph_exec_out);

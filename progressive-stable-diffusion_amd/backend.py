@@ -26,6 +26,18 @@ def _p(t: Optional[torch.Tensor]):
     return t.data_ptr()
 
 
+_SFX = {torch.float16: "f16", torch.bfloat16: "bf16"}
+
+
+def _sfx(*ts) -> str:
+    """Entry-point suffix for the 16-bit operands of one op: ``f16`` or ``bf16`` (the UNet's bf16 operand mode).  Every
+    16-bit tensor of the op must carry the same dtype; mixing fp16 and bf16 in one launch is an error."""
+    kinds = {t.dtype for t in ts if t is not None and t.dtype in _SFX}
+    if len(kinds) != 1:
+        raise ValueError(f"one op takes fp16 or bf16 operands, not {sorted(str(k) for k in kinds) or 'neither'}")
+    return _SFX[kinds.pop()]
+
+
 class HipBackend:
     name = "hip-gfx950"
 
@@ -118,15 +130,15 @@ class HipBackend:
         b, c, h, wd = x.shape
         assert x.dtype == torch.float32 and c <= 4 and w.shape[1:] == (9, 8) and out.shape == (b, h, wd, w.shape[0])
         assert gn_ws is None or (gn_ws.dtype == torch.float32 and gn_ws.numel() >= b * gn_nchunk * 64)
-        L.check(self.lib.dadd_conv_in_nchw_f16(_p(x), _p(w), _p(bias), _p(out), b, c, h, wd, w.shape[0],
-                                               _p(gn_ws), gn_nchunk, self.s))
+        fn = getattr(self.lib, "dadd_conv_in_nchw_" + _sfx(w, out))
+        L.check(fn(_p(x), _p(w), _p(bias), _p(out), b, c, h, wd, w.shape[0], _p(gn_ws), gn_nchunk, self.s))
 
     def conv_cout4(self, x, w, bias, out, mode=0):
         b, h, wd, c = x.shape
         co = w.shape[0]
         assert w.shape == (co, 9, c) and out.shape == (b, co, h, wd) and out.dtype == torch.float32
-        L.check(self.lib.dadd_conv3x3_cout4_f16(_p(x), _p(w), _p(bias), _p(out), b, h, wd, c, co,
-                                                int(mode), self.s))
+        fn = getattr(self.lib, "dadd_conv3x3_cout4_" + _sfx(x, w))
+        L.check(fn(_p(x), _p(w), _p(bias), _p(out), b, h, wd, c, co, int(mode), self.s))
 
     def conv_out_ddim(self, x, w, bias, latents, coef):
         """conv_out fused with the DDIM update: ``latents`` (fp32 NCHW) are stepped in place, eps is not stored."""
@@ -134,7 +146,8 @@ class HipBackend:
         co = w.shape[0]
         assert w.shape == (co, 9, c) and latents.shape == (b, co, h, wd) and latents.dtype == torch.float32 \
             and coef.numel() == 4 and coef.dtype == torch.float32
-        L.check(self.lib.dadd_conv_out_ddim_f16(_p(x), _p(w), _p(bias), _p(latents), _p(coef), b, h, wd, c, co, self.s))
+        fn = getattr(self.lib, "dadd_conv_out_ddim_" + _sfx(x, w))
+        L.check(fn(_p(x), _p(w), _p(bias), _p(latents), _p(coef), b, h, wd, c, co, self.s))
 
     def q_sample(self, x0, noise, t, alphas_cumprod, out):
         b = x0.shape[0]
@@ -169,6 +182,7 @@ class HipBackend:
         b, hi, wi, c1 = x.shape
         c2 = 0 if x2 is None else x2.shape[-1]
         n = w.shape[0]
+        fn = getattr(self.lib, "dadd_conv_igemm_" + _sfx(x, x2, w, out, residual, None if gn_apply is None else gn_apply[0]))
         ho, wo = out.shape[1], out.shape[2]
         assert w.shape[1] == taps * (c1 + c2), (w.shape, taps, c1, c2)
         assert out.shape[-1] == (n // 2 if flags & L.EPI_GEGLU else n) and out.shape[0] == b
@@ -213,12 +227,12 @@ class HipBackend:
         d.gn_out_eps = 0.0
         if gn_apply is not None:
             g_out, gam, bet, eps_o = gn_apply
-            assert flags & L.EPI_GNAPPLY and g_out.shape == out.shape and g_out.dtype == torch.float16 and g_out.is_contiguous() \
+            assert flags & L.EPI_GNAPPLY and g_out.shape == out.shape and g_out.dtype == out.dtype and g_out.is_contiguous() \
                 and gam.dtype == bet.dtype == torch.float32 and gam.numel() == n and bet.numel() == n
             d.gn_out, d.gn_out_gamma, d.gn_out_beta, d.gn_out_eps = _p(g_out), _p(gam), _p(bet), float(eps_o)
         if partial is not None:
             assert partial.numel() >= splitk * b * ho * wo * n
-        L.check(self.lib.dadd_conv_igemm_f16(C.byref(d), self.s))
+        L.check(fn(C.byref(d), self.s))
 
     def groupnorm(self, x1, x2, gamma, beta, out, ws, groups, eps, silu, ws_chunks=0):
         """``ws_chunks`` > 0: ``ws`` holds the chunk partials written by the producing GEMM's epilogue."""
@@ -228,29 +242,30 @@ class HipBackend:
         c2 = 0 if x2 is None else x2.shape[-1]
         need = (ws_chunks + (64 if ws_chunks > 128 else 0)) if ws_chunks else L.GN_MAX_CHUNKS
         assert out.shape[-1] == c1 + c2 and ws.numel() >= b * need * groups * 2
-        L.check(self.lib.dadd_groupnorm_f16(_p(x1), c1, _p(x2), c2, _p(gamma), _p(beta), _p(out),
-                                            _p(ws), b, hw, groups, float(eps), int(silu), int(ws_chunks), self.s))
+        fn = getattr(self.lib, "dadd_groupnorm_" + _sfx(x1, x2, out))
+        L.check(fn(_p(x1), c1, _p(x2), c2, _p(gamma), _p(beta), _p(out), _p(ws), b, hw, groups, float(eps), int(silu),
+                   int(ws_chunks), self.s))
 
     def layernorm(self, x, gamma, beta, out, eps=1e-5):
         c = x.shape[-1]
         m = x.numel() // c
-        L.check(self.lib.dadd_layernorm_f16(_p(x), _p(gamma), _p(beta), _p(out), m, c, float(eps),
-                                            self.s))
+        fn = getattr(self.lib, "dadd_layernorm_" + _sfx(x, out))
+        L.check(fn(_p(x), _p(gamma), _p(beta), _p(out), m, c, float(eps), self.s))
 
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""
         b, n, c3 = qkv.shape
         c = c3 // 3
         base = qkv.data_ptr()
-        L.check(self.lib.dadd_self_attn_f16(base, base + 2 * c, base + 4 * c, _p(out), b, n, heads,
-                                            c // heads, c3, out.stride(-2), self.s))
+        fn = getattr(self.lib, "dadd_self_attn_" + _sfx(qkv, out))
+        L.check(fn(base, base + 2 * c, base + 4 * c, _p(out), b, n, heads, c // heads, c3, out.stride(-2), self.s))
 
     def tri_xattn(self, q, kv, out, gates, lam, mode, heads, lam_dev=None):
         """``lam_dev`` (device float32[1]) overrides ``lam``: lambda is then a device-side parameter."""
         b, n, c = q.shape
-        L.check(self.lib.dadd_tri_xattn_f16(_p(q), _p(kv), _p(out), _p(gates), float(lam), _p(lam_dev), int(mode),
-                                            b, n, heads, c // heads, kv.shape[1], kv.stride(1),
-                                            self.s))
+        fn = getattr(self.lib, "dadd_tri_xattn_" + _sfx(q, kv, out))
+        L.check(fn(_p(q), _p(kv), _p(out), _p(gates), float(lam), _p(lam_dev), int(mode), b, n, heads, c // heads,
+                   kv.shape[1], kv.stride(1), self.s))
 
     def attn2_fused(self, x, mcat, vw, bias, residual, out, ln_stats_out=None, ln_stats_in=None, ln_c1=None, ln_d=None,
                     ln_eps=1e-5):
@@ -259,6 +274,8 @@ class HipBackend:
         with ``ln_c1`` / ``ln_d`` [B,384]: norm2 folded in (x un-normalised, mcat carrying gamma)."""
         b, hw, c = x.shape
         assert mcat.shape == (b, 384, c) and vw.shape == (b, c, 384) and out.shape == x.shape
+        if _sfx(x, mcat, vw, residual, out) != "f16":
+            raise ValueError("attn2_fused has no bf16 form: the bf16 plan takes the to_q + tri_xattn + to_out path")
         if ln_stats_out is not None:
             assert ln_stats_out.shape == (c // 80, b * hw, 2) and ln_stats_out.dtype == torch.float32 \
                 and ln_stats_out.is_contiguous()
@@ -317,8 +334,9 @@ class HipBackend:
         b, nq, c = out.shape
         nk = k.shape[1]
         assert q.shape[:2] == (b, nq) and v.shape[:2] == (b, nk) and k.stride(1) == v.stride(1)
-        L.check(self.lib.dadd_attn_f16(_p(q), _p(k), _p(v), _p(out), b, nq, nk, heads, c // heads, q.stride(1),
-                                       k.stride(1), out.stride(1), self.s))
+        fn = getattr(self.lib, "dadd_attn_" + _sfx(q, k, v, out))
+        L.check(fn(_p(q), _p(k), _p(v), _p(out), b, nq, nk, heads, c // heads, q.stride(1), k.stride(1), out.stride(1),
+                   self.s))
 
     def clip_patch_rows(self, pixels, out, patch):
         b, _, h, w = pixels.shape

@@ -13,6 +13,9 @@ int dadd_init_norm();
 int dadd_init_attn2_fused();
 int dadd_init_ffn_block();
 int dadd_init_tf_head();
+int dadd_init_igemm_bf16();      // the bf16 twins (*_bf16.hip)
+int dadd_init_attention_bf16();
+int dadd_init_norm_bf16();
 
 namespace {
 thread_local char g_err[512] = "";
@@ -62,6 +65,9 @@ int dadd_init(void) {
   if (rc == DADD_OK) rc = dadd_init_norm();
   if (rc == DADD_OK) rc = dadd_init_attn2_fused();
   if (rc == DADD_OK) rc = dadd_init_ffn_block();
+  if (rc == DADD_OK) rc = dadd_init_igemm_bf16();
+  if (rc == DADD_OK) rc = dadd_init_attention_bf16();
+  if (rc == DADD_OK) rc = dadd_init_norm_bf16();
   return rc != DADD_OK ? rc : dadd_init_tf_head();
 }
 

@@ -26,6 +26,12 @@ constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
 constexpr int v_stride(int dvp) { return ((dvp * 2) % 64 == 32) ? dvp : dvp + 16; }
 
 __device__ __forceinline__ h8 tr_pair(const half_t* lds_row_lo, const half_t* lds_row_hi) {
+#ifdef DADD_BF16
+  typedef __attribute__((address_space(3))) h4 lds_v4;
+  const h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_lo);
+  const h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_hi);
+  return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+#else
   typedef __attribute__((address_space(3))) fp16x4 lds_v4;
   const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_lo);
   const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_hi);
@@ -33,6 +39,7 @@ __device__ __forceinline__ h8 tr_pair(const half_t* lds_row_lo, const half_t* ld
   r[0] = (half_t)a[0]; r[1] = (half_t)a[1]; r[2] = (half_t)a[2]; r[3] = (half_t)a[3];
   r[4] = (half_t)b[0]; r[5] = (half_t)b[1]; r[6] = (half_t)b[2]; r[7] = (half_t)b[3];
   return r;
+#endif
 }
 
 __device__ __forceinline__ h8 pack_p(const f4& lo, const f4& hi) {
@@ -275,7 +282,7 @@ __global__ __launch_bounds__(NW * 64, DR <= 96 ? 2 : 1) void flash_kernel(const 
         const h8 ka = *reinterpret_cast<const h8*>(kp + kf * 1024);
 #pragma unroll
         for (int f = 0; f < QF; ++f)
-          sacc[kf][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka, qf[f][s], s == 0 ? negm[f] : sacc[kf][f], 0, 0, 0);
+          sacc[kf][f] = DADD_MFMA_16X16X32(ka, qf[f][s], s == 0 ? negm[f] : sacc[kf][f], 0, 0, 0);
       }
     }
 
@@ -368,7 +375,7 @@ __global__ __launch_bounds__(NW * 64, DR <= 96 ? 2 : 1) void flash_kernel(const 
         const h8 va = tr_pair(base, base + 16 * VLD);
 #pragma unroll
         for (int f = 0; f < QF; ++f)
-          oacc[df][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(va, pb[f][kb], oacc[df][f], 0, 0, 0);
+          oacc[df][f] = DADD_MFMA_16X16X32(va, pb[f][kb], oacc[df][f], 0, 0, 0);
       }
     }
     FSTAMP(4)   // V fragment reads + PV MFMAs issued
@@ -545,7 +552,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(const XattnArgs p) {
       sacc[f] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < KS; ++s)
-        sacc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kA[f][s], qB[s], sacc[f], 0, 0, 0);
+        sacc[f] = DADD_MFMA_16X16X32(kA[f][s], qB[s], sacc[f], 0, 0, 0);
     }
     // softmax over the 16 keys of each fragment (or over all NF*16 when JOINT)
     float mx[NF], sm[NF];
@@ -601,7 +608,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(const XattnArgs p) {
       f4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb)
-        o = __builtin_amdgcn_mfma_f32_16x16x32_f16(vA[df][kb], pb[kb], o, 0, 0, 0);
+        o = DADD_MFMA_16X16X32(vA[df][kb], pb[kb], o, 0, 0, 0);
       const int dcol = df * 16 + 4 * g;
       if (qok && dcol < DR) {
         h4 ov;
@@ -628,7 +635,7 @@ int launch_flash(const FlashArgs& a, hipStream_t s) {
   constexpr int smem = (PF ? 2 : 1) * (((D + 63) / 64) * 4096 + 64 * v_stride(DVP)) * (int)sizeof(half_t);
   constexpr int QB = NW * 16 * QF;
   dim3 grid(((a.Nq + QB - 1) / QB) * a.B * a.H);
-  static const std::string name = "flash_kernel<" + std::to_string(DR) + ", " + std::to_string(QF) + ", " + (PF ? "true" : "false") +
+  static const std::string name = DADD_KNAME("flash_kernel") "<" + std::to_string(DR) + ", " + std::to_string(QF) + ", " + (PF ? "true" : "false") +
                                   (NW == 4 ? "" : ", " + std::to_string(NW)) + ">";
   const double tok = (double)a.B * a.Nq, c = (double)a.H * DR;
   dadd_launch({name.c_str(), 4.0 * tok * a.N * c, (tok + (double)a.B * a.N) * c * 2.0 * 2.0}, flash_kernel<DR, QF, PF, NW>, grid, dim3(NW * 64), smem, s, a);
@@ -642,7 +649,7 @@ int launch_xattn(XattnArgs a, int mode, hipStream_t s) {
   // wave handles one 16-query fragment and the grid is four times as large
   a.qpb = ((long)a.B * a.H * ((a.N + 255) / 256) < 512) ? 64 : 256;
   dim3 grid((a.N + a.qpb - 1) / a.qpb, a.B * a.H);
-  static const std::string nm = "xattn_kernel<" + std::to_string(DR);
+  static const std::string nm = DADD_KNAME("xattn_kernel") "<" + std::to_string(DR);
   static const std::string n2t = nm + ", 2, true>", n3f = nm + ", 3, false>", n2f = nm + ", 2, false>";
   const double tok = (double)a.B * a.N, c = (double)a.C;
   const double bytes = tok * c * 4.0;
@@ -662,12 +669,16 @@ int dadd_init_attention() {
   int rc = flash_attr<40, 2, true>();
   if (rc == DADD_OK) rc = flash_attr<40, 4, true>();
   if (rc == DADD_OK) rc = flash_attr<40, 2, true, 8>();
+#ifndef DADD_BF16
   if (rc == DADD_OK) rc = flash_attr<64, 2, true>();
   if (rc == DADD_OK) rc = flash_attr<96, 1, true>();
+#endif
   if (rc == DADD_OK) rc = flash_attr<80, 2, true>();
   if (rc == DADD_OK) rc = flash_attr<160, 2, true>();
   if (rc == DADD_OK) rc = flash_attr<160, 1, true>();
+#ifndef DADD_BF16
   if (rc == DADD_OK) rc = flash_attr<512, 1, false>();
+#endif
   return rc;
 }
 
@@ -706,15 +717,24 @@ extern "C" int dadd_attn_f16(const void* q, const void* k, const void* v, void* 
       if ((long)B * heads * ((Nq + 255) / 256) >= 512) return var == 1 ? launch_flash<40, 2, true, 8>(a, s) : launch_flash<40, 4, true>(a, s);
       return launch_flash<40, 2, true>(a, s);
     }
+#ifndef DADD_BF16      // (the bf16 twin serves the UNet's head dims only: 40, 80, 160)
     case 64: return launch_flash<64, 2, true>(a, s);     // CLIP ViT towers (257 tokens, 16 x 64)
+#endif
     case 80: return launch_flash<80, 2, true>(a, s);     // (16 queries per wave measured slower at 32x32, B = 4: 29.7 against 27.2 us)
+#ifndef DADD_BF16
     case 96: return launch_flash<96, 1, true>(a, s);     // nn.MultiheadAttention(768, 8) of the resampler / purifier
+#endif
     case 160:   // 16 queries per wave while 32 would leave most of the chip idle (16x16 maps at B = 4: 64 -> 128 workgroups,
                 // 15.9 -> 10.7 us, profiles/r03_zi_flash_small.txt; two-wave workgroups measured 12.8)
       return ((long)B * heads * ((Nq + 127) / 128) < 256) ? launch_flash<160, 1, true>(a, s) : launch_flash<160, 2, true>(a, s);
+#ifndef DADD_BF16
     case 512: return launch_flash<512, 1, false>(a, s);
     default:
       dadd_set_error("attn: unsupported head dim %d (40, 64, 80, 96, 160, 512)", d);
+#else
+    default:
+      dadd_set_error("attn_bf16: no bf16 instantiation for head dim %d (40, 80, 160)", d);
+#endif
       return DADD_EINVAL;
   }
 }

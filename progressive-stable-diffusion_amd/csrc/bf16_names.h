@@ -1,0 +1,49 @@
+// Included first by every *_bf16.hip twin: selects the bf16 storage type (dadd_common.h) and gives the twin's kernels,
+// internal host functions and C entry points their own names, so that the fp16 source compiles a second time beside
+// itself in one library.  The fp16 build never sees this header.
+#pragma once
+#define DADD_BF16 1
+
+#define IgemmArgs IgemmArgs_bf16
+
+// kernels (rocprofv3 and the launch tags show the _bf16 names)
+#define igemm_kernel igemm_kernel_bf16
+#define splitk_finish_kernel splitk_finish_kernel_bf16
+#define splitk_finish_gn_kernel splitk_finish_gn_kernel_bf16
+#define splitk_finish_gnapply_kernel splitk_finish_gnapply_kernel_bf16
+#define igemm_dma_kernel igemm_dma_kernel_bf16
+#define conv3x3_halo_kernel conv3x3_halo_kernel_bf16
+#define gn_stats_kernel gn_stats_kernel_bf16
+#define gn_apply_kernel gn_apply_kernel_bf16
+#define gn_fused_kernel gn_fused_kernel_bf16
+#define gn_reduce_kernel gn_reduce_kernel_bf16
+#define layernorm_kernel layernorm_kernel_bf16
+#define flash_kernel flash_kernel_bf16
+#define xattn_kernel xattn_kernel_bf16
+#define conv_in_nchw_kernel conv_in_nchw_kernel_bf16
+#define conv_in_nchw_gn_kernel conv_in_nchw_gn_kernel_bf16
+#define conv_cout4_kernel conv_cout4_kernel_bf16
+
+// host functions shared between the GEMM sources and with api.hip
+#define dadd_init_igemm dadd_init_igemm_bf16
+#define dadd_init_igemm_dma dadd_init_igemm_dma_bf16
+#define dadd_launch_igemm_dma dadd_launch_igemm_dma_bf16
+#define dadd_igemm_dma_persistent dadd_igemm_dma_persistent_bf16
+#define dadd_init_conv_halo dadd_init_conv_halo_bf16
+#define dadd_conv_halo_applicable dadd_conv_halo_applicable_bf16
+#define dadd_conv_halo_gn_channels dadd_conv_halo_gn_channels_bf16
+#define dadd_launch_conv_halo dadd_launch_conv_halo_bf16
+#define dadd_init_norm dadd_init_norm_bf16
+#define dadd_init_attention dadd_init_attention_bf16
+
+// C entry points (include/dadd_hip.h)
+#define dadd_conv_igemm_f16 dadd_conv_igemm_bf16
+#define dadd_groupnorm_f16 dadd_groupnorm_bf16
+#define dadd_layernorm_f16 dadd_layernorm_bf16
+#define dadd_attn_f16 dadd_attn_bf16
+#define dadd_attn_debug dadd_attn_debug_bf16      // (diagnostics build only)
+#define dadd_self_attn_f16 dadd_self_attn_bf16
+#define dadd_tri_xattn_f16 dadd_tri_xattn_bf16
+#define dadd_conv_in_nchw_f16 dadd_conv_in_nchw_bf16
+#define dadd_conv3x3_cout4_f16 dadd_conv3x3_cout4_bf16
+#define dadd_conv_out_ddim_f16 dadd_conv_out_ddim_bf16

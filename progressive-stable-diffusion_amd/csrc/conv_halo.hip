@@ -345,7 +345,7 @@ __global__ __launch_bounds__(DUO ? 768 : 512, 1) void conv3x3_halo_kernel(const 
 #pragma unroll
       for (int k = 0; k < 4 * J; ++k) {
         const int jj = k / 4, ii = k % 4;
-        acc[jj][ii] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[jj], xa[ii], acc[jj][ii], 0, 0, 0);
+        acc[jj][ii] = DADD_MFMA_16X16X32(wb[jj], xa[ii], acc[jj][ii], 0, 0, 0);
         if (ii == 3) wb[jj] = *reinterpret_cast<const h8*>(wnext + jj * 2048);       // last use of wb[jj] this tap
         if (jj == J - 1)                                                             // last use of xa[ii] this tap
           xa[ii] = *reinterpret_cast<const h8*>(hbn + (addr_of(std::integral_constant<int, NT>{}, ii / FPL) ^ hx) + (ii % FPL) * 2048);
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(DUO ? 768 : 512, 1) void conv3x3_halo_kernel(const 
 #pragma unroll
     for (int k = 0; k < 4 * J; ++k) {               // K half 0; the half-1 fragments stream in behind
       const int jj = k / 4, ii = k % 4;
-      acc[jj][ii] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb0[jj], xa0[ii], acc[jj][ii], 0, 0, 0);
+      acc[jj][ii] = DADD_MFMA_16X16X32(wb0[jj], xa0[ii], acc[jj][ii], 0, 0, 0);
       if (k == 0) wb1[0] = *reinterpret_cast<const h8*>(wcur1);
       else if (k <= 4) xa1[k - 1] = *reinterpret_cast<const h8*>(hb + (addr_of(std::integral_constant<int, T>{}, (k - 1) / FPL) ^ 64) + ((k - 1) % FPL) * 2048);
       else if (k < 4 + J) wb1[k - 4] = *reinterpret_cast<const h8*>(wcur1 + (k - 4) * 2048);
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(DUO ? 768 : 512, 1) void conv3x3_halo_kernel(const 
 #pragma unroll
     for (int k = 0; k < 4 * J; ++k) {               // K half 1; prefetch of the next tap's half 0
       const int jj = k / 4, ii = k % 4;
-      acc[jj][ii] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb1[jj], xa1[ii], acc[jj][ii], 0, 0, 0);
+      acc[jj][ii] = DADD_MFMA_16X16X32(wb1[jj], xa1[ii], acc[jj][ii], 0, 0, 0);
       if (k == 0) wb0[0] = *reinterpret_cast<const h8*>(wnext);
       else if (k <= 4) xa0[k - 1] = *reinterpret_cast<const h8*>(hbn + addr_of(std::integral_constant<int, NT>{}, (k - 1) / FPL) + ((k - 1) % FPL) * 2048);
       else if (k < 4 + J) wb0[k - 4] = *reinterpret_cast<const h8*>(wnext + (k - 4) * 2048);
@@ -552,17 +552,17 @@ int dadd_launch_conv_halo(const IgemmArgs& a, int nsplit, hipStream_t s) {
   const double flop = dadd_igemm_flop(a), bytes = dadd_igemm_bytes(a);
   const bool duo = (a.flags & DADD_TUNE_SHALLOW) != 0;   // A/B switch: measured equal to the one-wave build (see the kernel comment)
   if (a.flags & DADD_PRE_GN) {
-    if (a.Wo == 64) dadd_launch({"conv3x3_halo_kernel<64, false, true>", flop, bytes}, conv3x3_halo_kernel<64, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
-    else if (a.Wo == 32) dadd_launch({"conv3x3_halo_kernel<32, false, true>", flop, bytes}, conv3x3_halo_kernel<32, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
-    else dadd_launch({"conv3x3_halo_kernel<16, false, true>", flop, bytes}, conv3x3_halo_kernel<16, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
+    if (a.Wo == 64) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<64, false, true>", flop, bytes}, conv3x3_halo_kernel<64, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
+    else if (a.Wo == 32) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<32, false, true>", flop, bytes}, conv3x3_halo_kernel<32, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
+    else dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<16, false, true>", flop, bytes}, conv3x3_halo_kernel<16, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
   } else if (duo) {
-    if (a.Wo == 64) dadd_launch({"conv3x3_halo_kernel<64, true, false>", flop, bytes}, conv3x3_halo_kernel<64, true>, grid, dim3(768), SMEM_BYTES, s, a);
-    else if (a.Wo == 32) dadd_launch({"conv3x3_halo_kernel<32, true, false>", flop, bytes}, conv3x3_halo_kernel<32, true>, grid, dim3(768), SMEM_BYTES, s, a);
-    else dadd_launch({"conv3x3_halo_kernel<16, true, false>", flop, bytes}, conv3x3_halo_kernel<16, true>, grid, dim3(768), SMEM_BYTES, s, a);
+    if (a.Wo == 64) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<64, true, false>", flop, bytes}, conv3x3_halo_kernel<64, true>, grid, dim3(768), SMEM_BYTES, s, a);
+    else if (a.Wo == 32) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<32, true, false>", flop, bytes}, conv3x3_halo_kernel<32, true>, grid, dim3(768), SMEM_BYTES, s, a);
+    else dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<16, true, false>", flop, bytes}, conv3x3_halo_kernel<16, true>, grid, dim3(768), SMEM_BYTES, s, a);
   } else {
-    if (a.Wo == 64) dadd_launch({"conv3x3_halo_kernel<64, false, false>", flop, bytes}, conv3x3_halo_kernel<64, false>, grid, dim3(512), SMEM_BYTES, s, a);
-    else if (a.Wo == 32) dadd_launch({"conv3x3_halo_kernel<32, false, false>", flop, bytes}, conv3x3_halo_kernel<32, false>, grid, dim3(512), SMEM_BYTES, s, a);
-    else dadd_launch({"conv3x3_halo_kernel<16, false, false>", flop, bytes}, conv3x3_halo_kernel<16, false>, grid, dim3(512), SMEM_BYTES, s, a);
+    if (a.Wo == 64) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<64, false, false>", flop, bytes}, conv3x3_halo_kernel<64, false>, grid, dim3(512), SMEM_BYTES, s, a);
+    else if (a.Wo == 32) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<32, false, false>", flop, bytes}, conv3x3_halo_kernel<32, false>, grid, dim3(512), SMEM_BYTES, s, a);
+    else dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<16, false, false>", flop, bytes}, conv3x3_halo_kernel<16, false>, grid, dim3(512), SMEM_BYTES, s, a);
   }
   DADD_LAUNCH_CHECK();
   return DADD_OK;

@@ -1,0 +1,3 @@
+// bf16 twin of conv_halo.hip: the same kernels with bf16 storage (dadd_common.h), named *_bf16 (bf16_names.h).
+#include "bf16_names.h"
+#include "conv_halo.hip"

@@ -7,10 +7,28 @@
 
 #include "../../include/dadd_hip.h"
 
+// ---- 16-bit storage type ----------------------------------------------------------------------
+// half_t / h8 / h4 / h2 are the storage type of activations and packed weights: fp16 as the sources are written, bf16
+// when a *_bf16.hip twin defines DADD_BF16 and includes the same source (the UNet's bf16 operand mode).  The MFMA
+// (16x16x32), the 2-wide dot product and the float -> 16-bit casts follow the type; on gfx950 the bf16 forms run at the
+// same rate with the same lane maps and C/D layout, and (__bf16)float rounds to nearest even (v_cvt_pk_bf16_f32).
+// Accumulation and statistics stay fp32 in both.  The twin renames its kernels and entry points (suffix _bf16) before
+// the include; DADD_KNAME gives the launch tags the same suffix.
+#ifdef DADD_BF16
+typedef __bf16 half_t;
+typedef __bf16 h8 __attribute__((ext_vector_type(8)));
+typedef __bf16 h4 __attribute__((ext_vector_type(4)));
+typedef __bf16 h2 __attribute__((ext_vector_type(2)));
+#define DADD_MFMA_16X16X32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
+#define DADD_KNAME(s) s "_bf16"
+#else
 typedef _Float16 half_t;
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+#define DADD_MFMA_16X16X32 __builtin_amdgcn_mfma_f32_16x16x32_f16
+#define DADD_KNAME(s) s
+#endif
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -63,6 +81,14 @@ inline void dadd_launch(const DaddLaunchTag& tag, void (*kernel)(KA...), dim3 gr
 }
 
 // ---- device helpers -------------------------------------------------------------------------
+// c + a[0] * b[0] + a[1] * b[1] in one v_dot2 (exact 16-bit products, fp32 sum) on the storage type
+__device__ __forceinline__ float dadd_fdot2(h2 a, h2 b, float c) {
+#ifdef DADD_BF16
+  return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false);
+#else
+  return __builtin_amdgcn_fdot2(a, b, c, false);
+#endif
+}
 // x * sigmoid(x) with the hardware reciprocal (1 ulp) instead of an IEEE division (ten instructions): GroupNorm + SiLU
 // runs per element in gn_apply and, inside the 3x3 conv, on the loader waves of conv3x3_halo_kernel
 __device__ __forceinline__ float dadd_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

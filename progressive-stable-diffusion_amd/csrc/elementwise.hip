@@ -4,6 +4,7 @@
 
 namespace {
 
+#ifndef DADD_BF16   // (the bf16 twin, elementwise_bf16.hip, carries the UNet's conv_in / conv_out only)
 // fp32 NCHW (C<=8 real channels) -> fp16 NHWC8, optional per-pixel CxC matrix + bias, then scale
 __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ x, half_t* __restrict__ out,
                                                    int B, int C, int HW, float scale,
@@ -69,6 +70,8 @@ __global__ __launch_bounds__(256) void conv_cin8_kernel(const half_t* __restrict
   *reinterpret_cast<h8*>(out + (size_t)pix * Cout + co0) = r;
 }
 
+#endif  // !DADD_BF16
+
 // conv_in of the UNet straight from the fp32 NCHW latents (C <= 4 channels): the layout change + fp16 rounding of
 // pack_kernel happens in registers (same rounding point), two v_dot2_f32_f16 per tap and output channel instead of
 // 24 converts + multiply-adds over the zero-padded 8 channels.  thread = (pixel, group of 8 output channels); the
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void conv_cin8_kernel(const half_t* __restrict
 __global__ __launch_bounds__(256) void conv_in_nchw_kernel(const float* __restrict__ x, const half_t* __restrict__ w,
                                                            const float* __restrict__ bias, half_t* __restrict__ out,
                                                            int B, int C, int H, int W, int Cout) {
-  typedef _Float16 ci_h2 __attribute__((ext_vector_type(2)));
+  typedef half_t ci_h2 __attribute__((ext_vector_type(2)));
   const int HW = H * W, npix = B * HW;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int co0 = blockIdx.y * 8;
@@ -92,8 +95,8 @@ __global__ __launch_bounds__(256) void conv_in_nchw_kernel(const float* __restri
     float v[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) v[c] = (c < C && ok) ? xp[(size_t)c * HW] : 0.f;
-    x01[tap] = ci_h2{(_Float16)v[0], (_Float16)v[1]};
-    x23[tap] = ci_h2{(_Float16)v[2], (_Float16)v[3]};
+    x01[tap] = ci_h2{(half_t)v[0], (half_t)v[1]};
+    x23[tap] = ci_h2{(half_t)v[2], (half_t)v[3]};
   }
   h8 r;
 #pragma unroll
@@ -102,8 +105,8 @@ __global__ __launch_bounds__(256) void conv_in_nchw_kernel(const float* __restri
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const h4 wv = *reinterpret_cast<const h4*>(w + ((size_t)(co0 + o) * 9 + tap) * 8);
-      acc = __builtin_amdgcn_fdot2(x01[tap], ci_h2{wv[0], wv[1]}, acc, false);
-      acc = __builtin_amdgcn_fdot2(x23[tap], ci_h2{wv[2], wv[3]}, acc, false);
+      acc = dadd_fdot2(x01[tap], ci_h2{wv[0], wv[1]}, acc);
+      acc = dadd_fdot2(x23[tap], ci_h2{wv[2], wv[3]}, acc);
     }
     r[o] = (half_t)acc;
   }
@@ -119,7 +122,7 @@ template <int CG>
 __global__ __launch_bounds__(256) void conv_in_nchw_gn_kernel(const float* __restrict__ x, const half_t* __restrict__ w,
                                                               const float* __restrict__ bias, half_t* __restrict__ out,
                                                               float* __restrict__ gn_ws, int B, int C, int H, int W, int Cout) {
-  typedef _Float16 ci_h2 __attribute__((ext_vector_type(2)));
+  typedef half_t ci_h2 __attribute__((ext_vector_type(2)));
   static_assert((4 * CG) % 8 == 0, "four groups must be whole 8-channel stores");
   __shared__ float red[4][8];
   const int HW = H * W;
@@ -135,8 +138,8 @@ __global__ __launch_bounds__(256) void conv_in_nchw_gn_kernel(const float* __res
     float v[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) v[c] = (c < C && ok) ? xp[(size_t)c * HW] : 0.f;
-    x01[tap] = ci_h2{(_Float16)v[0], (_Float16)v[1]};
-    x23[tap] = ci_h2{(_Float16)v[2], (_Float16)v[3]};
+    x01[tap] = ci_h2{(half_t)v[0], (half_t)v[1]};
+    x23[tap] = ci_h2{(half_t)v[2], (half_t)v[3]};
   }
   float st[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (sum, sum of squares) of the four groups
 #pragma unroll
@@ -149,8 +152,8 @@ __global__ __launch_bounds__(256) void conv_in_nchw_gn_kernel(const float* __res
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const h4 wv = *reinterpret_cast<const h4*>(w + ((size_t)co * 9 + tap) * 8);
-        acc = __builtin_amdgcn_fdot2(x01[tap], ci_h2{wv[0], wv[1]}, acc, false);
-        acc = __builtin_amdgcn_fdot2(x23[tap], ci_h2{wv[2], wv[3]}, acc, false);
+        acc = dadd_fdot2(x01[tap], ci_h2{wv[0], wv[1]}, acc);
+        acc = dadd_fdot2(x23[tap], ci_h2{wv[2], wv[3]}, acc);
       }
       r[o] = (half_t)acc;
       const float f = (float)r[o];
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(256) void conv_in_nchw_gn_kernel(const float* __res
 // lane) and multiplied with v_dot2_f32_f16 (exact fp16 products, fp32 sums).  The weights [Cout][9][C] are staged in
 // LDS once per block.  (The first version — one pixel per thread, a tap loop with early-outs, converts + fma — took
 // 50 us for the UNet's 320 -> 4 conv_out at 4x64x64: as long as a 3x3 conv with 80x the flops.)
-typedef _Float16 cc_h2 __attribute__((ext_vector_type(2)));
+typedef half_t cc_h2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void conv_cout4_kernel(const half_t* __restrict__ x,
                                                          const half_t* __restrict__ w,
                                                          const float* __restrict__ bias,
@@ -234,8 +237,8 @@ __global__ __launch_bounds__(256) void conv_cout4_kernel(const half_t* __restric
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const cc_h2 wp = {wv[2 * c], wv[2 * c + 1]};
-            a0[o] = __builtin_amdgcn_fdot2(cc_h2{xv[0][tap][2 * c], xv[0][tap][2 * c + 1]}, wp, a0[o], false);
-            a1[o] = __builtin_amdgcn_fdot2(cc_h2{xv[1][tap][2 * c], xv[1][tap][2 * c + 1]}, wp, a1[o], false);
+            a0[o] = dadd_fdot2(cc_h2{xv[0][tap][2 * c], xv[0][tap][2 * c + 1]}, wp, a0[o]);
+            a1[o] = dadd_fdot2(cc_h2{xv[1][tap][2 * c], xv[1][tap][2 * c + 1]}, wp, a1[o]);
           }
         }
       }
@@ -279,6 +282,7 @@ __global__ __launch_bounds__(256) void conv_cout4_kernel(const half_t* __restric
   }
 }
 
+#ifndef DADD_BF16
 __global__ void timestep_features_kernel(const int64_t* __restrict__ t, float* __restrict__ out, int M,
                                          int dim) {
   const int half = dim / 2;
@@ -475,8 +479,11 @@ __global__ __launch_bounds__(256) void mse_rows_kernel(const float* __restrict__
   if (threadIdx.x == 0) out[b] = (red[0] + red[1] + red[2] + red[3]) / (float)per;
 }
 
+#endif  // !DADD_BF16
+
 }  // namespace
 
+#ifndef DADD_BF16
 extern "C" int dadd_q_sample_f32(const float* x0, const float* noise, const int64_t* t, const float* alphas_cumprod,
                                  float* out, int B, int64_t per_sample, void* stream) {
   DADD_REQUIRE(x0 && noise && t && alphas_cumprod && out && B > 0 && per_sample > 0, "q_sample: bad arguments");
@@ -551,6 +558,8 @@ extern "C" int dadd_conv3x3_cin8_f16(const void* x, const void* w, const float* 
   return DADD_OK;
 }
 
+#endif  // !DADD_BF16
+
 extern "C" int dadd_conv_in_nchw_f16(const float* x_nchw, const void* w, const float* bias, void* out, int B, int C,
                                     int H, int W, int Cout, float* gn_ws, int gn_nchunk, void* stream) {
   DADD_REQUIRE(x_nchw && w && out, "conv_in_nchw: null pointer");
@@ -562,13 +571,13 @@ extern "C" int dadd_conv_in_nchw_f16(const float* x_nchw, const void* w, const f
     DADD_REQUIRE(Cout == 320 && (H * W) % 256 == 0 && gn_nchunk == (H * W) / 256 && gn_nchunk <= DADD_GN_MAX_CHUNKS,
                  "conv_in_nchw: GroupNorm partials need Cout == 320, H*W %% 256 == 0 and gn_nchunk == H*W/256 (<= %d)",
                  DADD_GN_MAX_CHUNKS);
-    dadd_launch({"conv_in_nchw_gn_kernel", 2.0 * npix * Cout * 9.0 * C, (double)npix * (4.0 * C + 2.0 * Cout)},
+    dadd_launch({DADD_KNAME("conv_in_nchw_gn_kernel"), 2.0 * npix * Cout * 9.0 * C, (double)npix * (4.0 * C + 2.0 * Cout)},
                 conv_in_nchw_gn_kernel<10>, dim3(npix / 256, Cout / 40), dim3(256), 0, static_cast<hipStream_t>(stream),
                 x_nchw, static_cast<const half_t*>(w), bias, static_cast<half_t*>(out), gn_ws, B, C, H, W, Cout);
     DADD_LAUNCH_CHECK();
     return DADD_OK;
   }
-  dadd_launch({"conv_in_nchw_kernel", 2.0 * npix * Cout * 9.0 * C, (double)npix * (4.0 * C + 2.0 * Cout)}, conv_in_nchw_kernel,
+  dadd_launch({DADD_KNAME("conv_in_nchw_kernel"), 2.0 * npix * Cout * 9.0 * C, (double)npix * (4.0 * C + 2.0 * Cout)}, conv_in_nchw_kernel,
               dim3((npix + 255) / 256, Cout / 8), dim3(256), 0, static_cast<hipStream_t>(stream), x_nchw,
               static_cast<const half_t*>(w), bias, static_cast<half_t*>(out), B, C, H, W, Cout);
   DADD_LAUNCH_CHECK();
@@ -590,7 +599,7 @@ static int conv_cout4_launch(const void* x, const void* w, const float* bias, fl
                                  (int)smem));
     smem_set = smem;
   }
-  dadd_launch({"conv_cout4_kernel", 2.0 * npix * Cout * 9.0 * C, (double)npix * (2.0 * C + 4.0 * Cout)}, conv_cout4_kernel, dim3((npix + 31) / 32), dim3(256), smem,
+  dadd_launch({DADD_KNAME("conv_cout4_kernel"), 2.0 * npix * Cout * 9.0 * C, (double)npix * (2.0 * C + 4.0 * Cout)}, conv_cout4_kernel, dim3((npix + 31) / 32), dim3(256), smem,
                      static_cast<hipStream_t>(stream), static_cast<const half_t*>(x),
                      static_cast<const half_t*>(w), bias, out_nchw, B, H, W, C, Cout, mode, coef);
   DADD_LAUNCH_CHECK();
@@ -609,6 +618,7 @@ extern "C" int dadd_conv_out_ddim_f16(const void* x, const void* w, const float*
   return conv_cout4_launch(x, w, bias, latents, B, H, W, C, Cout, 3, coef, stream);
 }
 
+#ifndef DADD_BF16
 extern "C" int dadd_timestep_features_f32(const int64_t* t, float* out, int M, int dim, void* stream) {
   DADD_REQUIRE(t && out && M > 0 && dim > 0 && dim % 2 == 0, "timestep_features: bad arguments");
   const int n = M * dim / 2;
@@ -656,3 +666,4 @@ extern "C" int dadd_ddim_update_f32(float* x, const float* eps_c, const float* e
   DADD_LAUNCH_CHECK();
   return DADD_OK;
 }
+#endif  // !DADD_BF16

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs p) {
       for (int j = 0; j < J; ++j)
 #pragma unroll
         for (int i = 0; i < MI; ++i)
-          acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[j], xa[i], acc[j][i], 0, 0, 0);
+          acc[j][i] = DADD_MFMA_16X16X32(wb[j], xa[i], acc[j][i], 0, 0, 0);
     }
   };
 
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void splitk_finish_gn_kernel(const IgemmArgs p
 template <int VEC>
 __global__ __launch_bounds__(512) void splitk_finish_gnapply_kernel(const IgemmArgs p, int nsplit) {
   typedef float fv __attribute__((ext_vector_type(VEC)));
-  typedef _Float16 hv __attribute__((ext_vector_type(VEC)));
+  typedef half_t hv __attribute__((ext_vector_type(VEC)));
   extern __shared__ __attribute__((aligned(16))) char fg_smem[];
   half_t* slab = reinterpret_cast<half_t*>(fg_smem);       // [HW][cg]
   __shared__ float red[2][4];
@@ -431,7 +431,7 @@ int launch(const IgemmArgs& a, int nsplit, hipStream_t s) {
   constexpr int smem = 2 * (BM + BN) * BK * (int)sizeof(half_t) + (BM == 128 ? (BN == 160 ? 8192 : LN_LDS_BYTES) : 4096);   // + the epilogue's scratch
   const int mtiles = (a.M + BM - 1) / BM;
   dim3 grid(mtiles * a.ntiles, nsplit);
-  static const std::string name = "igemm_kernel<" + std::to_string(BM) + ", " + std::to_string(BN) + ", " + (DEEP ? "true" : "false") + ">";
+  static const std::string name = DADD_KNAME("igemm_kernel") "<" + std::to_string(BM) + ", " + std::to_string(BN) + ", " + (DEEP ? "true" : "false") + ">";
   dadd_launch({name.c_str(), dadd_igemm_flop(a), dadd_igemm_bytes(a)}, igemm_kernel<BM, BN, DEEP>, grid, dim3(256), smem, s, a);
   DADD_LAUNCH_CHECK();
   return DADD_OK;
@@ -673,10 +673,10 @@ extern "C" int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream) {
     int blocks = (int)((total + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     const int ns = halo ? halo_ns : nsplit;
-    const DaddLaunchTag tag = {(a.flags & DADD_EPI_GNSTAT) ? "splitk_finish_gn_kernel" : "splitk_finish_kernel", 0.0,
+    const DaddLaunchTag tag = {(a.flags & DADD_EPI_GNSTAT) ? DADD_KNAME("splitk_finish_gn_kernel") : DADD_KNAME("splitk_finish_kernel"), 0.0,
                                (double)a.M * a.N * (4.0 * ns + 2.0 + ((a.flags & DADD_EPI_RESIDUAL) ? 2.0 : 0.0))};
     if (a.flags & DADD_EPI_GNAPPLY) {
-      const DaddLaunchTag tag2 = {"splitk_finish_gnapply_kernel", 0.0, tag.bytes + 2.0 * a.M * a.N};
+      const DaddLaunchTag tag2 = {DADD_KNAME("splitk_finish_gnapply_kernel"), 0.0, tag.bytes + 2.0 * a.M * a.N};
       const unsigned slab_bytes = (unsigned)(a.Ho * a.Wo * (a.N / 32) * 2);
       if ((a.N / 32) % 4 == 0 && a.ldo % 4 == 0 && a.ldr % 4 == 0 && a.ld_rowvec % 4 == 0)
         dadd_launch(tag2, splitk_finish_gnapply_kernel<4>, dim3(32, a.B), dim3(512), slab_bytes, s, a, ns);

@@ -99,12 +99,12 @@ static inline double dadd_igemm_bytes(const IgemmArgs& a) {
 // lane accumulates sum x and sum x^2 of the 8-element pieces it reads anyway (v_dot2_f32_f16: exact products, fp32
 // sums), and two xor-shuffles over the four k-quarters of a fragment finish the row — whose outputs that same lane
 // owns in the swapped-MFMA layout.  No statistics pass, no normalised copy of the activation, no extra launch.
-typedef _Float16 dadd_h2 __attribute__((ext_vector_type(2)));
+typedef half_t dadd_h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void ln_acc_pair(const h8& x, int p, float& s1, float& s2) {
   const dadd_h2 v = {x[2 * p], x[2 * p + 1]};
-  const dadd_h2 one = {(_Float16)1.0f, (_Float16)1.0f};
-  s1 = __builtin_amdgcn_fdot2(v, one, s1, false);
-  s2 = __builtin_amdgcn_fdot2(v, v, s2, false);
+  const dadd_h2 one = {(half_t)1.0f, (half_t)1.0f};
+  s1 = dadd_fdot2(v, one, s1);
+  s2 = dadd_fdot2(v, v, s2);
 }
 template <int MI>
 __device__ __forceinline__ void ln_finish(float (&s1)[MI], float (&s2)[MI], int K, float eps) {   // -> mu, rstd

@@ -356,7 +356,7 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
 #pragma unroll
       for (int k = 0; k < MI * J; ++k) {     // first K half; the second half's fragments stream in behind
         const int jj = k / MI, ii = k % MI;
-        acc[jj][ii] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb0[jj], xa0[ii], acc[jj][ii], 0, 0, 0);
+        acc[jj][ii] = DADD_MFMA_16X16X32(wb0[jj], xa0[ii], acc[jj][ii], 0, 0, 0);
         if constexpr (LNF) {
 #pragma unroll
           for (int t2 = 0; t2 < LPER; ++t2)
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
 #pragma unroll
       for (int k = 0; k < MI * J; ++k) {     // second K half; prefetch of tile it+1's first half
         const int jj = k / MI, ii = k % MI;
-        acc[jj][ii] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb1[jj], xa1[ii], acc[jj][ii], 0, 0, 0);
+        acc[jj][ii] = DADD_MFMA_16X16X32(wb1[jj], xa1[ii], acc[jj][ii], 0, 0, 0);
         if constexpr (LNF) {
 #pragma unroll
           for (int t2 = 0; t2 < LPER; ++t2)
@@ -475,23 +475,23 @@ int dadd_launch_igemm_dma(const IgemmArgs& a, int tile_m, int tile_n, int nsplit
                "igemm(dma): operand larger than the 2 GiB buffer window");
   if (tile_m == 128 && dadd_igemm_dma_persistent(a, nsplit)) {
     dim3 grid(g_num_cu);
-    if (tile_n == 160) { static const char* const nm[3] = {"igemm_dma_kernel<128, 160, false, true, 0>", "igemm_dma_kernel<128, 160, false, true, 1>", "igemm_dma_kernel<128, 160, false, true, 2>"}; launch<128, 160, false, true>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {"igemm_dma_kernel<128, 128, false, true, 0>", "igemm_dma_kernel<128, 128, false, true, 1>", "igemm_dma_kernel<128, 128, false, true, 2>"}; launch<128, 128, false, true>(nm, a, grid, s); }
+    if (tile_n == 160) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 160, false, true, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, true, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, true, 2>"}; launch<128, 160, false, true>(nm, a, grid, s); }
+    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 128, false, true, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, true, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, true, 2>"}; launch<128, 128, false, true>(nm, a, grid, s); }
     DADD_LAUNCH_CHECK();
     return DADD_OK;
   }
   dim3 grid(total, nsplit);
   if (tile_m == 64) {
     DADD_REQUIRE(!a.ups, "igemm(dma): the 64-row tiles have no upsample gather");
-    if (tile_n == 160) { static const char* const nm[3] = {"igemm_dma_kernel<64, 160, false, false, 0>", "igemm_dma_kernel<64, 160, false, false, 1>", "igemm_dma_kernel<64, 160, false, false, 2>"}; launch<64, 160, false, false>(nm, a, grid, s); }
-    else if (tile_n == 128) { static const char* const nm[3] = {"igemm_dma_kernel<64, 128, false, false, 0>", "igemm_dma_kernel<64, 128, false, false, 1>", "igemm_dma_kernel<64, 128, false, false, 2>"}; launch<64, 128, false, false>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {"igemm_dma_kernel<64, 64, false, false, 0>", "igemm_dma_kernel<64, 64, false, false, 1>", "igemm_dma_kernel<64, 64, false, false, 2>"}; launch<64, 64, false, false>(nm, a, grid, s); }
+    if (tile_n == 160) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<64, 160, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<64, 160, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<64, 160, false, false, 2>"}; launch<64, 160, false, false>(nm, a, grid, s); }
+    else if (tile_n == 128) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<64, 128, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<64, 128, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<64, 128, false, false, 2>"}; launch<64, 128, false, false>(nm, a, grid, s); }
+    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<64, 64, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<64, 64, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<64, 64, false, false, 2>"}; launch<64, 64, false, false>(nm, a, grid, s); }
   } else if (tile_n == 160) {
-    if (a.ups) { static const char* const nm[3] = {"igemm_dma_kernel<128, 160, true, false, 0>", "igemm_dma_kernel<128, 160, true, false, 1>", "igemm_dma_kernel<128, 160, true, false, 2>"}; launch<128, 160, true, false>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {"igemm_dma_kernel<128, 160, false, false, 0>", "igemm_dma_kernel<128, 160, false, false, 1>", "igemm_dma_kernel<128, 160, false, false, 2>"}; launch<128, 160, false, false>(nm, a, grid, s); }
+    if (a.ups) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 160, true, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 160, true, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 160, true, false, 2>"}; launch<128, 160, true, false>(nm, a, grid, s); }
+    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 160, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, false, 2>"}; launch<128, 160, false, false>(nm, a, grid, s); }
   } else {
-    if (a.ups) { static const char* const nm[3] = {"igemm_dma_kernel<128, 128, true, false, 0>", "igemm_dma_kernel<128, 128, true, false, 1>", "igemm_dma_kernel<128, 128, true, false, 2>"}; launch<128, 128, true, false>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {"igemm_dma_kernel<128, 128, false, false, 0>", "igemm_dma_kernel<128, 128, false, false, 1>", "igemm_dma_kernel<128, 128, false, false, 2>"}; launch<128, 128, false, false>(nm, a, grid, s); }
+    if (a.ups) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 128, true, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 128, true, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 128, true, false, 2>"}; launch<128, 128, true, false>(nm, a, grid, s); }
+    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 128, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, false, 2>"}; launch<128, 128, false, false>(nm, a, grid, s); }
   }
   DADD_LAUNCH_CHECK();
   return DADD_OK;

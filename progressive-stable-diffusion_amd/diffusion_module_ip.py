@@ -308,8 +308,14 @@ class DiffusionModuleWithIP:
     def __init__(self, cfg: Any, state_dict: Optional[Dict[str, torch.Tensor]] = None, *,
                  device=None, seed: int = 0, batch_size: Optional[int] = None,
                  clip_config: Optional[dict] = None, backend=None, warm_start_dis: bool = True,
-                 _strict: Optional[bool] = None, _report=None):
+                 operand_dtype: torch.dtype = torch.float16, _strict: Optional[bool] = None, _report=None):
+        """``operand_dtype``: 16-bit storage of every UNet plan and DdimLoop of the module, ``torch.float16`` (default)
+        or ``torch.bfloat16`` (fp32's exponent range; fp32 accumulation either way).  The conditioning front-end and
+        the VAE are fp16 in both modes and hand fp32 across to the UNet."""
         from .backend import HipBackend
+        if operand_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"operand_dtype must be torch.float16 or torch.bfloat16, got {operand_dtype!r}")
+        self.operand_dtype = operand_dtype
         self.cfg = cfg
         self.diff_cfg = diff_cfg_from(cfg)
         dc = self.diff_cfg
@@ -390,7 +396,7 @@ class DiffusionModuleWithIP:
         if u is None:
             dc = self.diff_cfg
             plan = UNetPlan(self.be, self._sd, batch, side, use_routing_gates=dc.use_routing_gates,
-                            use_frequency_strategy=dc.use_frequency_strategy)
+                            use_frequency_strategy=dc.use_frequency_strategy, dtype=self.operand_dtype)
             u = OrdinalUNet(plan, dc.use_routing_gates, self.cfg.model.conditioning_dim,
                             self.cfg.model.latent_channels, self.cfg.model.latent_channels)
             if self._unets:     # keep delta_scale consistent across plans
@@ -417,7 +423,8 @@ class DiffusionModuleWithIP:
         reference's inference loads), ``current_model_state`` the raw ones (``which="raw"``).  ``strict=False``
         (the reference's call, inference_pipeline_ip.py:587-592) tolerates missing / unexpected keys and reports
         them in ``module.load_report``.  Only loaders that execute nothing from the file are used, whatever
-        ``weights_only`` says."""
+        ``weights_only`` says.  Keyword arguments go to the constructor (``device``, ``batch_size``,
+        ``operand_dtype``, ...)."""
         from . import checkpoint as CK
         from .config import to_attr
         sd, rep, blob = CK.load_state(str(checkpoint_path), which=which)
@@ -434,7 +441,7 @@ class DiffusionModuleWithIP:
         for a in args:
             if isinstance(a, (torch.device, str)) and torch.device(a).type != self.device.type:
                 raise RuntimeError(f"this module lives on {self.device}; there is no {a} path")
-        return self            # storage precision is fixed by the engine (fp16 tiles, fp32 accumulate)
+        return self            # storage precision is fixed by the engine (operand_dtype tiles, fp32 accumulate)
 
     def half(self):
         return self

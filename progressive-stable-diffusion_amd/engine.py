@@ -29,7 +29,8 @@ import torch
 from . import lib as L
 from .routing import get_block_type  # noqa: F401  (re-exported for callers)
 
-F16, F32 = torch.float16, torch.float32
+F16, F32, BF16 = torch.float16, torch.float32, torch.bfloat16
+OPERAND_DTYPES = (F16, BF16)     # 16-bit storage of the UNet plan: fp16 (default) or bf16 (csrc/*_bf16.hip)
 UNET_CH = (320, 640, 1280, 1280)
 VAE_CH = (128, 256, 512, 512)
 HEADS = 8
@@ -43,26 +44,26 @@ A2_MIN_TILES = int(os.environ.get("DADD_A2_MIN_TILES", "128"))
 
 
 # ----------------------------------------------------------------------------- weight packing
-def pack_conv(w: torch.Tensor) -> torch.Tensor:
-    """[Cout,Cin,kh,kw] (or [Cout,Cin]) fp32 -> [Cout, kh*kw*Cin] fp16, K = (tap, cin)."""
+def pack_conv(w: torch.Tensor, dtype=F16) -> torch.Tensor:
+    """[Cout,Cin,kh,kw] (or [Cout,Cin]) fp32 -> [Cout, kh*kw*Cin] fp16 (or ``dtype``), K = (tap, cin)."""
     if w.dim() == 2:
-        return w.to(F16).contiguous()
+        return w.to(dtype).contiguous()
     co, ci, kh, kw = w.shape
-    return w.permute(0, 2, 3, 1).reshape(co, kh * kw * ci).to(F16).contiguous()
+    return w.permute(0, 2, 3, 1).reshape(co, kh * kw * ci).to(dtype).contiguous()
 
 
-def pack_conv_cin8(w: torch.Tensor) -> torch.Tensor:
-    """[Cout,Cin<=8,3,3] -> [Cout,9,8] fp16, input channels zero-padded to 8."""
+def pack_conv_cin8(w: torch.Tensor, dtype=F16) -> torch.Tensor:
+    """[Cout,Cin<=8,3,3] -> [Cout,9,8] fp16 (or ``dtype``), input channels zero-padded to 8."""
     co, ci, _, _ = w.shape
-    out = torch.zeros(co, 9, 8, dtype=F16)
-    out[:, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, 9, ci).to(F16)
+    out = torch.zeros(co, 9, 8, dtype=dtype)
+    out[:, :, :ci] = w.permute(0, 2, 3, 1).reshape(co, 9, ci).to(dtype)
     return out.contiguous()
 
 
-def pack_conv_cout4(w: torch.Tensor) -> torch.Tensor:
-    """[Cout<=4,C,3,3] -> [Cout,9,C] fp16."""
+def pack_conv_cout4(w: torch.Tensor, dtype=F16) -> torch.Tensor:
+    """[Cout<=4,C,3,3] -> [Cout,9,C] fp16 (or ``dtype``)."""
     co, ci, _, _ = w.shape
-    return w.permute(0, 2, 3, 1).reshape(co, 9, ci).to(F16).contiguous()
+    return w.permute(0, 2, 3, 1).reshape(co, 9, ci).to(dtype).contiguous()
 
 
 def geglu_interleave(w: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -77,12 +78,12 @@ def geglu_interleave(w: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, to
     return w[src].contiguous(), b[src].contiguous()
 
 
-def fold_layernorm(w: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor):
+def fold_layernorm(w: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, dtype=F16):
     """LayerNorm folded into the linear that consumes it (csrc/igemm_args.h, DADD_EPI_LNFOLD):
     LN(x) W^T + b = rstd (x (gamma o W)^T - mu c1) + (W beta + b).  Returns (gamma o W in fp16, c1, composed bias);
     c1 sums the ROUNDED weights, so that the mean term cancels exactly against what the MFMAs accumulate."""
     w, gamma, beta = w.double(), gamma.double(), beta.double()
-    w16 = (w * gamma[None, :]).to(F16)
+    w16 = (w * gamma[None, :]).to(dtype)
     bias = w @ beta + (b.double() if b is not None else 0.0)
     return w16, w16.double().sum(dim=1).float(), bias.float()
 
@@ -274,13 +275,15 @@ def plan_tiling(m, n, k, taps, geglu, residual, ups=0, stride=1) -> Tuple[int, i
 class Pool:
     """Plan-time buffer pool: fixed addresses, explicit release, reuse by (shape, dtype)."""
 
-    def __init__(self, be):
+    def __init__(self, be, dtype=F16):
         self.be = be
+        self.dtype = dtype              # of get() without an explicit dtype: the plan's 16-bit activations
         self.free: Dict[Tuple, List[torch.Tensor]] = {}
         self.bytes = 0
         self.on_put = None
 
-    def get(self, shape, dtype=F16) -> torch.Tensor:
+    def get(self, shape, dtype=None) -> torch.Tensor:
+        dtype = dtype or self.dtype
         key = (tuple(shape), dtype)
         lst = self.free.get(key)
         if lst:
@@ -298,10 +301,13 @@ class Pool:
 
 
 class _Plan:
-    def __init__(self, be, wcache=None):
+    def __init__(self, be, wcache=None, dtype=F16):
+        if dtype not in OPERAND_DTYPES:
+            raise ValueError(f"plan dtype must be torch.float16 or torch.bfloat16, got {dtype}")
         self.be = be
         self.wcache = wcache
-        self.pool = Pool(be)
+        self.dtype = dtype              # 16-bit storage of activations and packed weights
+        self.pool = Pool(be, dtype)
         self.ops: List = []
         self.keep: List[torch.Tensor] = []  # weights & persistent buffers
         self.gn_partials: Dict[int, Tuple[torch.Tensor, int]] = {}   # output buffer -> (chunk partials, chunks)
@@ -336,7 +342,9 @@ class _Plan:
 
     def cached(self, key, make):
         """Device tensor for ``key`` from the optional cross-plan cache (``wcache``: plans for other batch sizes
-        or tilings over the same state dict share the packed weights instead of re-packing 1.9 GB each)."""
+        or tilings over the same state dict share the packed weights instead of re-packing 1.9 GB each).  The key carries
+        the plan's dtype: fp16 and bf16 plans over one cache never hand each other their packed weights."""
+        key = (*key, self.dtype)
         if self.wcache is None:         # plan-local memo: one device copy per key (fuse_gn hints name the same tensors twice)
             t = self._memo.get(key)
             if t is None:
@@ -469,8 +477,12 @@ class UNetPlan(_Plan):
     """SD-1.x UNet forward for a fixed (B, S); eps = plan(latents) with cond/time prepared apart."""
 
     def __init__(self, be, sd: Dict[str, torch.Tensor], batch: int, side: int, *,
-                 prefix="unet.unet", use_routing_gates=True, use_frequency_strategy=True, wcache=None):
-        super().__init__(be, wcache)
+                 prefix="unet.unet", use_routing_gates=True, use_frequency_strategy=True, wcache=None, dtype=F16):
+        """``dtype``: 16-bit storage of activations, packed weights, conditioning and K/V caches (fp32 accumulation either
+        way).  bf16 takes the generic path at the sites where fp16 uses a row-block fusion (tf_head, ffn_block,
+        attn2_fused have no bf16 form); every other tiling / split-K / fold choice is the fp16 plan's.  The time-embedding
+        rows stay as in fp16 (fp32 rows from fp16 weights, dadd_linear_rows_f32)."""
+        super().__init__(be, wcache, dtype)
         assert side % 8 == 0, "latent side must be a multiple of 8 (three stride-2 levels)"
         self.B, self.S = batch, side
         self.gates_mode = use_routing_gates
@@ -510,16 +522,16 @@ class UNetPlan(_Plan):
                                                          sd[ap + ".processor.dis_gate"]]).float())
             else:
                 self.gates[site] = None
-            self.kv_w[site] = self.dev(torch.cat(ws), F16)
-            self.kv[site] = [be.zeros((batch, 1, self.T, self.kv_w[site].shape[0]), F16)
+            self.kv_w[site] = self.dev(torch.cat(ws), dtype)
+            self.kv[site] = [be.zeros((batch, 1, self.T, self.kv_w[site].shape[0]), dtype)
                              for _ in range(2)]                     # [cond, uncond]
-        self.cond16 = be.zeros((batch, 1, self.T, 768), F16)
+        self.cond16 = be.zeros((batch, 1, self.T, 768), dtype)
         self.kv_slot = 0
         self.cond_gen = 0      # advanced by every set_cond(): callers that cache projections key on it
         # ---- attn2 folded into ONE kernel per block (dadd_attn2_fused_f16): with 16 keys per pathway
         # q K^T = x (W_q K^T) and P V W_o^T = P (V W_o^T), so the step-invariant conditioning absorbs both
         # projections.  Sites whose map is smaller than one 128-token tile (8x8) keep the three-kernel path.
-        self.fused_attn2 = bool(use_routing_gates) and FUSED_ATTN2
+        self.fused_attn2 = bool(use_routing_gates) and FUSED_ATTN2 and dtype == F16
         self.a2, self._a2_dirty, self._a2_lam = {}, True, None
         if self.fused_attn2:
             for site, c in self.sites:
@@ -594,7 +606,7 @@ class UNetPlan(_Plan):
         return s
 
     def w(self, key, pack=pack_conv):
-        return self.cached((self.prefix + key, pack.__name__), lambda: self.dev(pack(self.sd[self.prefix + key])))
+        return self.cached((self.prefix + key, pack.__name__), lambda: self.dev(pack(self.sd[self.prefix + key], self.dtype)))
 
     def f(self, key):
         return self.cached((self.prefix + key, "f32"), lambda: self.dev(self.sd[self.prefix + key].float()))
@@ -649,7 +661,8 @@ class UNetPlan(_Plan):
         def make():
             w = torch.cat([self.sd[u + tb + k] for k in wkey_list])
             b = self.sd[u + tb + bias_key] if bias_key else None
-            w16, c1, bias = fold_layernorm(w, b, self.sd[u + tb + norm + ".weight"], self.sd[u + tb + norm + ".bias"])
+            w16, c1, bias = fold_layernorm(w, b, self.sd[u + tb + norm + ".weight"], self.sd[u + tb + norm + ".bias"],
+                                           self.dtype)
             if geglu:               # row order of the fused GEGLU epilogue; c1 / bias follow their rows
                 idx = geglu_interleave(torch.arange(w16.shape[0])[:, None].float(), torch.zeros(w16.shape[0]))[0][:, 0].long()
                 w16, c1, bias = w16[idx], c1[idx], bias[idx]
@@ -666,9 +679,10 @@ class UNetPlan(_Plan):
         m_rows = b * h * w_
         fold1, fold2, fold3 = (fold_here(m_rows, 3 * c, c), fold_here(m_rows, c, c) and site not in self.a2,
                                fold_here(m_rows, 8 * c, c, True))
-        fused_tail = FUSED_FFN and c == 320 and (h * w_) % 64 == 0 and m_rows // 64 >= FFN_MIN_BLOCKS
+        rowblock = self.dtype == F16          # (the row-block fusions have no bf16 form)
+        fused_tail = rowblock and FUSED_FFN and c == 320 and (h * w_) % 64 == 0 and m_rows // 64 >= FFN_MIN_BLOCKS
         xpart = self.gn_partials.get(x.data_ptr())
-        fused_head = (FUSED_HEAD and c == 320 and (h * w_) % 64 == 0 and m_rows // 64 >= FFN_MIN_BLOCKS
+        fused_head = (rowblock and FUSED_HEAD and c == 320 and (h * w_) % 64 == 0 and m_rows // 64 >= FFN_MIN_BLOCKS
                       and xpart is not None and xpart[1] <= 256)
         ext = LN_STATS_FROM_PRODUCER and LN_FOLD == "auto"
         if fused_head:               # norm -> proj_in -> norm1 -> q|k|v in one launch (csrc/tf_head.hip)
@@ -706,7 +720,7 @@ class UNetPlan(_Plan):
                             ln_stats_in=None if fold1 else st1)
         else:
             wqkv = self.cached((self.prefix + tb, "qkv"), lambda: self.dev(
-                torch.cat([self.sd[self.prefix + tb + f".attn1.to_{n}.weight"] for n in "qkv"]), F16))
+                torch.cat([self.sd[self.prefix + tb + f".attn1.to_{n}.weight"] for n in "qkv"]), self.dtype))
             qkv = self.conv(ln_of(hs, ".norm1"), wqkv, (b, h, w_, 3 * c), taps=1, pad=0)
         att = self.pool.get(shp)
         self.rec(self.be.self_attn, qkv.view(b, h * w_, 3 * c), att.view(b, h * w_, c), HEADS)
@@ -782,7 +796,7 @@ class UNetPlan(_Plan):
             def _geglu():
                 wf, bf = geglu_interleave(self.sd[self.prefix + tb + ".ff.net.0.proj.weight"],
                                           self.sd[self.prefix + tb + ".ff.net.0.proj.bias"])
-                return self.dev(wf, F16), self.dev(bf.float())
+                return self.dev(wf, self.dtype), self.dev(bf.float())
             wf, bf = self.cached((self.prefix + tb, "geglu"), _geglu)
             if self.wcache is not None:
                 self.keep += [wf, bf]

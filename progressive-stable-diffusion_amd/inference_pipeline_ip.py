@@ -33,6 +33,9 @@ def _apply_leace(image_embeds: Tensor, leace: dict) -> Tensor:
     return (flat + mu[None, :]).reshape(b, t, d)
 
 
+PRECISIONS = {"fp16": torch.float16, "bf16": torch.bfloat16}     # --precision -> DiffusionModuleWithIP(operand_dtype=)
+
+
 def _parse_args(argv=None) -> argparse.Namespace:
     """Same flags and defaults as the reference CLI (:60-162)."""
     p = argparse.ArgumentParser(description="Generate MES progression with patient-specific anatomical structure.")
@@ -51,6 +54,8 @@ def _parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--source-label", type=float, default=None)
     p.add_argument("--steer-scale", type=float, default=0.0)
     p.add_argument("--guidance-scale", type=float, default=None)
+    p.add_argument("--precision", choices=("fp16", "bf16"), default="fp16",
+                   help="16-bit storage of the UNet (fp32 accumulation either way); bf16 keeps fp32's exponent range")
     return p.parse_args(argv)
 
 
@@ -313,7 +318,8 @@ def main(argv=None) -> None:
     cfg = _load_config(args.config)
     target_steps = args.mes_steps
     module = DiffusionModuleWithIP.load_from_checkpoint(str(args.checkpoint), cfg=cfg, weights_only=False,
-                                                        strict=False, device=device, batch_size=target_steps)
+                                                        strict=False, device=device, batch_size=target_steps,
+                                                        operand_dtype=PRECISIONS[args.precision])
     module = module.to(device).to(torch.float32)
     module.eval()
     structure_tensor, display_tensor = _load_and_preprocess_structure_image(

@@ -13,7 +13,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdadd_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ffn_block.hip", "tf_head.hip", "norm.hip", "attention.hip", "elementwise.hip",
-           "conditioning.hip", "api.hip")
+           "conditioning.hip", "api.hip",
+           # bf16 twins of the UNet's generic-path kernels (csrc/bf16_names.h)
+           "igemm_bf16.hip", "igemm_dma_bf16.hip", "conv_halo_bf16.hip", "norm_bf16.hip", "attention_bf16.hip",
+           "elementwise_bf16.hip")
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -76,6 +79,20 @@ PROTOTYPES = {
     "dadd_clip_patch_rows_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "dadd_aoe_interp_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "dadd_purifier_tail_f16": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
+    # bf16 siblings: same argument lists as the _f16 entry points
+    "dadd_conv_igemm_bf16": (C.c_int, [C.POINTER(IgemmDesc), vp]),
+    "dadd_conv_in_nchw_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    "dadd_conv3x3_cout4_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, vp]),
+    "dadd_conv_out_ddim_bf16": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "dadd_groupnorm_bf16": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
+                                      C.c_int, f32, C.c_int, C.c_int, vp]),
+    "dadd_layernorm_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
+    "dadd_self_attn_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, vp]),
+    "dadd_attn_bf16": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 8 + [vp]),
+    "dadd_tri_xattn_bf16": (C.c_int, [vp, vp, vp, vp, f32, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, vp]),
     "dadd_begin_step": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "dadd_ddim_update_f32": (C.c_int, [vp, vp, vp, f32, vp, vp, i64, vp]),
     "dadd_prefetch": (C.c_int, [vp, i64, vp]),

@@ -21,6 +21,9 @@ def main():
     ap.add_argument("--image-size", type=int, default=512)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--vae", action="store_true")
+    ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16", help="16-bit storage of the UNet plan")
+    ap.add_argument("--passes", type=int, default=0,
+                    help="also time this many captured 50-step sampler passes (wall clock, after one warm-up pass)")
     ap.add_argument("--list", action="store_true", help="also print every launch of the last step in issue order")
     ap.add_argument("--out", default=None)
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
@@ -62,7 +65,7 @@ def main():
 
     if not a.vae:
         sd = W.init_state_dict(W.unet_shapes(), 0, gates=gates)
-        plan = UNetPlan(be, sd, a.batch, side)
+        plan = UNetPlan(be, sd, a.batch, side, dtype={"fp16": torch.float16, "bf16": torch.bfloat16}[a.dtype])
         loop = DdimLoop(plan)
         g = torch.Generator().manual_seed(0)
         plan.set_cond((torch.randn(a.batch, 48, 768, generator=g) * 0.5).to(dev), 0)
@@ -76,7 +79,20 @@ def main():
         be.prof_begin()
         for _ in range(a.steps):
             loop._one_step(3.0, False, 1.0)
-        report(f"UNet step B={a.batch} {a.image_size}x{a.image_size}", be.prof_end(), a.steps)
+        report(f"UNet step B={a.batch} {a.image_size}x{a.image_size} {a.dtype}", be.prof_end(), a.steps)
+        if a.passes:
+            import time
+            times = []
+            for i in range(a.passes + 1):
+                be.copy_(plan.lat_in, torch.randn(a.batch, 4, side, side, generator=g).to(dev))
+                be.synchronize()
+                t0 = time.perf_counter()
+                loop.run(3.0)
+                be.synchronize()
+                if i:
+                    times.append(time.perf_counter() - t0)
+            emit(f"== captured 50-step pass B={a.batch} {a.image_size}x{a.image_size} {a.dtype}: "
+                 f"median {1e3 * sorted(times)[len(times) // 2]:.1f} ms, min {1e3 * min(times):.1f} ms over {len(times)}")
     else:
         sd = W.init_state_dict(W.vae_shapes(encoder=False), 0)
         plan = VaeDecoderPlan(be, sd, a.batch, side)
