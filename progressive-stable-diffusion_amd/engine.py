@@ -21,7 +21,6 @@ computed once per sampling run.
 from __future__ import annotations
 
 import math
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -38,9 +37,9 @@ GROUPS = 32
 N_CU = 256
 # attn2 folded into one kernel (csrc/attn2_fused.hip).  Used where one launch has at least A2_MIN_TILES 128-token
 # tiles (B=4: the 64x64 sites; same-box A/B +0.9 % end to end); on the smaller maps its 32 / 8 workgroups leave the
-# chip idle (-6 % when forced everywhere), so those keep to_q + xattn + to_out.  DADD_FUSED_ATTN2=0 switches it off.
-FUSED_ATTN2 = os.environ.get("DADD_FUSED_ATTN2", "1") == "1"
-A2_MIN_TILES = int(os.environ.get("DADD_A2_MIN_TILES", "128"))
+# chip idle (-6 % when forced everywhere), so those keep to_q + xattn + to_out.  FUSED_ATTN2 = False switches it off.
+FUSED_ATTN2 = True
+A2_MIN_TILES = 128
 
 
 # ----------------------------------------------------------------------------- weight packing
@@ -159,7 +158,7 @@ FINISH_GN_APPLY = True
 # MEASURED AND OFF (profiles/r03_zh_weight_prefetch_ab.txt, same box, A B A B): 385.7 / 385.0 ms per pass without, 535.4 /
 # 534.8 ms with - a captured graph with ~80 side branches per step makes hipGraphLaunch host-bound (host queue time 277 ->
 # 504 ms per pass), far more than the 3-8 us per launch that hot weights save (profiles/r03_zg_cold_hot_weights.txt).
-WEIGHT_PREFETCH_AHEAD = int(os.environ.get("DADD_WEIGHT_PREFETCH", "0"))
+WEIGHT_PREFETCH_AHEAD = 0
 WEIGHT_PREFETCH_MIN_BYTES = 2 * 1024 * 1024
 
 # GroupNorm statistics written by the producing GEMM's epilogue (no gn_stats launch, one read of the tensor less).
@@ -301,26 +300,21 @@ class Pool:
 
 
 class _Plan:
-    def __init__(self, be, wcache=None, dtype=F16):
+    def __init__(self, be, wcache=None, dtype=F16, sd=None, prefix=""):
         if dtype not in OPERAND_DTYPES:
             raise ValueError(f"plan dtype must be torch.float16 or torch.bfloat16, got {dtype}")
         self.be = be
         self.wcache = wcache
         self.dtype = dtype              # 16-bit storage of activations and packed weights
+        self.sd, self.prefix = sd, prefix + "."
         self.pool = Pool(be, dtype)
         self.ops: List = []
         self.keep: List[torch.Tensor] = []  # weights & persistent buffers
         self.gn_partials: Dict[int, Tuple[torch.Tensor, int]] = {}   # output buffer -> (chunk partials, chunks)
         self.ln_partials: Dict[int, torch.Tensor] = {}               # output buffer -> LayerNorm row partials [P][M][2]
-
         self._memo: Dict = {}
         self.gn_ready: Dict[int, Tuple] = {}      # output buffer -> (its GroupNorm written by the finish kernel, gamma, beta, eps, silu)
-
-        def _forget(t):                 # a recycled buffer loses its statistics
-            self.gn_partials.pop(t.data_ptr(), None)
-            self.ln_partials.pop(t.data_ptr(), None)
-            self.gn_ready.pop(t.data_ptr(), None)
-        self.pool.on_put = _forget
+        self.pool.on_put = self._forget
         self.gn_ws = None
         # Split-K slabs are combined by the finish kernel.  The in-launch combine (last-arriving slice
         # reduces; `counters` of dadd_conv_igemm_f16) is implemented and tested but measured 2-4x SLOWER
@@ -335,27 +329,88 @@ class _Plan:
         for fn, a, k in self.ops:
             fn(*a, **k)
 
+    def _forget(self, t):
+        """``pool.on_put``: a recycled buffer loses its statistics.  A normalised copy of it (``gn_ready``) must have been
+        taken by then: only the consuming ``gn()`` hands that pool buffer on, so dropping the entry would leak it."""
+        assert t.data_ptr() not in self.gn_ready, f"GroupNorm of a {tuple(t.shape)} buffer written by a finish kernel, never consumed"
+        self.gn_partials.pop(t.data_ptr(), None)
+        self.ln_partials.pop(t.data_ptr(), None)
+
+    def _end_build(self, prefetch_weights=False):
+        """Every ``_build`` ends here."""
+        assert not self.gn_ready, f"GroupNorm written by a finish kernel, never consumed: {[tuple(r[0].shape) for r in self.gn_ready.values()]}"
+        if prefetch_weights:
+            self._insert_weight_prefetch()
+
+    def _insert_weight_prefetch(self):
+        """Every layer's weights are cold when its kernel starts (1.76 GB per step against 256 MB of Infinity Cache).  A
+        launch whose weights are at least WEIGHT_PREFETCH_MIN_BYTES gets a ``be.prefetch`` of them WEIGHT_PREFETCH_AHEAD
+        weight-bearing launches earlier - a side branch of the captured graph (``dadd_prefetch``) - and the plan ends with
+        the join.  Reads only: results are unchanged."""
+        if not WEIGHT_PREFETCH_AHEAD:
+            return
+        wops = []                       # (op index, weight tensor) of the launches that stream a weight operand
+        for i, (fn, a, k) in enumerate(self.ops):
+            name = getattr(fn, "__name__", "")
+            if name == "igemm":
+                wops.append((i, a[1]))
+            elif name in ("ffn_block", "tf_head"):
+                wops.append((i, a[1]))
+        inserts = []
+        for j, (i, w) in enumerate(wops):
+            if w.numel() * w.element_size() < WEIGHT_PREFETCH_MIN_BYTES or j < WEIGHT_PREFETCH_AHEAD:
+                continue
+            inserts.append((wops[j - WEIGHT_PREFETCH_AHEAD][0], w))
+        for at, w in sorted(inserts, key=lambda t: -t[0]):       # back to front: earlier indices stay valid
+            self.ops.insert(at, (self.be.prefetch, (w,), {}))
+        if inserts:
+            self.ops.append((self.be.prefetch_join, (), {}))
+
     def dev(self, t, dtype=None):
+        """A parameter or I/O buffer the plan uploads directly (not shared between plans)."""
         d = self.be.to_device(t, dtype)
         self.keep.append(d)
         return d
 
     def cached(self, key, make):
-        """Device tensor for ``key`` from the optional cross-plan cache (``wcache``: plans for other batch sizes
-        or tilings over the same state dict share the packed weights instead of re-packing 1.9 GB each).  The key carries
+        """Packed device tensor(s) for ``key``: ``make()`` uploads one tensor or a tuple (``be.to_device``) on the first
+        request - of any plan that shares the optional cross-plan cache (``wcache``: plans for other batch sizes or tilings
+        over the same state dict share the packed weights instead of re-packing 1.9 GB each).  The plan-local memo gives one
+        entry per key (fuse_gn hints name the same tensors twice) and puts each tensor into ``keep`` once.  The key carries
         the plan's dtype: fp16 and bf16 plans over one cache never hand each other their packed weights."""
         key = (*key, self.dtype)
-        if self.wcache is None:         # plan-local memo: one device copy per key (fuse_gn hints name the same tensors twice)
-            t = self._memo.get(key)
-            if t is None:
-                t = self._memo[key] = make()
-            return t
-        t = self.wcache.get(key)
+        t = self._memo.get(key)
         if t is None:
-            t = self.wcache[key] = make()
-        else:
-            self.keep.append(t)
+            t = self.wcache.get(key) if self.wcache is not None else None
+            if t is None:
+                t = make()
+                if self.wcache is not None:
+                    self.wcache[key] = t
+            self._memo[key] = t
+            self.keep += t if isinstance(t, tuple) else (t,)
         return t
+
+    def w(self, key, pack=pack_conv):
+        return self.cached((self.prefix + key, pack.__name__),
+                           lambda: self.be.to_device(pack(self.sd[self.prefix + key], self.dtype)))
+
+    def f(self, key):
+        return self.cached((self.prefix + key, "f32"), lambda: self.be.to_device(self.sd[self.prefix + key].float()))
+
+    def _gn_partials_for(self, out, nchunk, extra=0):
+        """GroupNorm chunk partials [B][nchunk + extra][32][2] of ``out``, written by the launch that takes the returned
+        keywords and found by the consumers of ``out`` in ``gn_partials``."""
+        ws = self.be.zeros((out.shape[0] * (nchunk + extra) * GROUPS * 2,), F32)
+        self.keep.append(ws)
+        self.gn_partials[out.data_ptr()] = (ws, nchunk)
+        return dict(gn_ws=ws, gn_nchunk=nchunk)
+
+    def _ln_partials_for(self, out, parts):
+        """LayerNorm row partials [parts][M][2] of ``out`` (DADD_EPI_LNSTAT), found by its folded consumer in ``ln_partials``."""
+        st = self.be.zeros((parts, out.numel() // out.shape[-1], 2), F32)
+        self.keep.append(st)
+        self.ln_partials[out.data_ptr()] = st
+        return st
 
     # ---- recorded building blocks -----------------------------------------------------------
     def conv(self, x, w, out_shape, *, x2=None, bias=None, rowvec=None, residual=None, taps=9,
@@ -396,18 +451,11 @@ class _Plan:
             # (> 128 chunks — the VAE maps — are folded to 64 per sample by gn_reduce_kernel inside dadd_groupnorm_f16:
             # one small launch instead of a statistics pass over the tensor; `ws` carries the room for them)
             if ok and howo % wm_rows == 0 and nchunk >= 1 and howo * cg * 2 > GN_FUSED_MAX_BYTES:
-                extra = 64 if nchunk > 128 else 0
-                ws = self.be.zeros((out_shape[0] * (nchunk + extra) * GROUPS * 2,), F32)
-                self.keep.append(ws)
-                self.gn_partials[out.data_ptr()] = (ws, nchunk)
-                gkw = dict(gn_ws=ws, gn_nchunk=nchunk)
+                gkw = self._gn_partials_for(out, nchunk, extra=64 if nchunk > 128 else 0)
                 flags |= L.EPI_GNSTAT
         if (ln_stats and LN_STATS_FROM_PRODUCER and not (flags & (L.EPI_GEGLU | L.EPI_GNSTAT)) and sk == 1
                 and n % (tile_n // 2) == 0 and n // (tile_n // 2) <= LN_STATS_MAX_PARTS):
-            st = self.be.zeros((n // (tile_n // 2), m, 2), F32)
-            self.keep.append(st)
-            self.ln_partials[out.data_ptr()] = st
-            gkw["ln_stats_out"] = st
+            gkw["ln_stats_out"] = self._ln_partials_for(out, n // (tile_n // 2))
             flags |= L.EPI_LNSTAT
         f = flags | (L.EPI_BIAS if bias is not None else 0) | (L.EPI_ROWVEC if rowvec is not None else 0) \
             | (L.EPI_RESIDUAL if residual is not None else 0) | (L.EPI_LNFOLD if ln_c1 is not None else 0) | tune
@@ -482,12 +530,10 @@ class UNetPlan(_Plan):
         way).  bf16 takes the generic path at the sites where fp16 uses a row-block fusion (tf_head, ffn_block,
         attn2_fused have no bf16 form); every other tiling / split-K / fold choice is the fp16 plan's.  The time-embedding
         rows stay as in fp16 (fp32 rows from fp16 weights, dadd_linear_rows_f32)."""
-        super().__init__(be, wcache, dtype)
+        super().__init__(be, wcache, dtype, sd, prefix)
         assert side % 8 == 0, "latent side must be a multiple of 8 (three stride-2 levels)"
         self.B, self.S = batch, side
         self.gates_mode = use_routing_gates
-        self.prefix = prefix + "."
-        self.sd = sd
         self.lam = 0.0
         # device-side scalars read by the kernels of a captured step: [0] = lambda (delta steering), [1] = CFG scale
         self.params = be.zeros((2,), F32)
@@ -544,8 +590,8 @@ class UNetPlan(_Plan):
                         mcat=be.zeros((batch, 384, c), F16), vw=be.zeros((batch, c, 384), F16),
                         # norm2 folded into the score GEMM (set by _transformer when the producer supplies row partials)
                         fold=False, ln_c1=be.zeros((batch, 384), F32), ln_d=be.zeros((batch, 384), F32),
-                        gamma=self.dev(sd[f"{u}{site}.transformer_blocks.0.norm2.weight"].float()),
-                        beta=self.dev(sd[f"{u}{site}.transformer_blocks.0.norm2.bias"].float()))
+                        gamma=self.f(f"{site}.transformer_blocks.0.norm2.weight"),
+                        beta=self.f(f"{site}.transformer_blocks.0.norm2.bias"))
         # The fold runs once per conditioning (every sampler pass): sites of equal width share ONE set of batched torch
         # ops over stacked weights / buffers (five sites at 64x64: ~25 launches instead of ~125, profiles/r03_*_pass_breakdown)
         self.a2_groups = []
@@ -605,16 +651,32 @@ class UNetPlan(_Plan):
         s += [(f"up_blocks.{i}.attentions.{j}", UNET_CH[3 - i]) for i in (1, 2, 3) for j in range(3)]
         return s
 
-    def w(self, key, pack=pack_conv):
-        return self.cached((self.prefix + key, pack.__name__), lambda: self.dev(pack(self.sd[self.prefix + key], self.dtype)))
-
-    def f(self, key):
-        return self.cached((self.prefix + key, "f32"), lambda: self.dev(self.sd[self.prefix + key].float()))
-
     # -- blocks ----------------------------------------------------------------------------------
     def _gn_of(self, key, eps, silu):
         """(gamma, beta, eps, silu) of the GroupNorm ``key`` — the ``fuse_gn`` hint of the conv that feeds it."""
         return (self.f(key + ".weight"), self.f(key + ".bias"), eps, silu)
+
+    def _norm_conv(self, name, n, x, skip, cout, release_x=False, **kw):
+        """``conv<n>(SiLU(norm<n>(x | skip)))`` of ResNet ``name``: the GroupNorm runs inside the 3x3 conv where the halo
+        kernel can apply it (``gn_in_conv_ok``), else through ``gn()``.  ``release_x``: ``x`` returns to the pool right after
+        its last reader is recorded - in the second arm BEFORE the conv, whose output may then take its place."""
+        b, h, w_, _ = x.shape
+        shp = (b, h, w_, cout)
+        w = self.w(f"{name}.conv{n}.weight")
+        norm = self._gn_of(f"{name}.norm{n}", 1e-5, 1)
+        kw.update(bias=self.f(f"{name}.conv{n}.bias"), gn_stats=True)
+        part = self.gn_in_conv_ok(x, skip, w, shp, kw.get("residual"))
+        if part is not None:         # (part carries the skip's partials too when there is one)
+            out = self.conv(x, w, shp, x2=skip, gn_in=tuple(part[:2]) + norm + tuple(part[2:]), **kw)
+            if release_x:
+                self.pool.put(x)
+        else:
+            g = self.gn(x, skip, *norm)
+            if release_x:
+                self.pool.put(x)
+            out = self.conv(g, w, shp, **kw)
+            self.pool.put(g)
+        return out
 
     def _resnet(self, name, x, skip=None, next_gn=None):
         """``next_gn``: the GroupNorm that consumes this block's output first (``_gn_of``), if the caller knows it."""
@@ -622,34 +684,15 @@ class UNetPlan(_Plan):
         cin = x.shape[-1] + (0 if skip is None else skip.shape[-1])
         cout = self.sd[self.prefix + name + ".conv1.weight"].shape[0]
         off = self.temb_off[name]
-        w1 = self.w(name + ".conv1.weight")
-        p1 = self.gn_in_conv_ok(x, skip, w1, (b, h, w_, cout), None)
-        if p1 is not None:           # norm1 + SiLU inside conv1 (p1 carries the skip's partials too when there is one)
-            h1 = self.conv(x, w1, (b, h, w_, cout), x2=skip, bias=self.f(name + ".conv1.bias"),
-                           rowvec=self.temb_rows[:, off:off + cout], gn_stats=True, fuse_gn=self._gn_of(name + ".norm2", 1e-5, 1),
-                           gn_in=(p1[0], p1[1], self.f(name + ".norm1.weight"), self.f(name + ".norm1.bias"), 1e-5, 1) + tuple(p1[2:]))
-        else:
-            g1 = self.gn(x, skip, self.f(name + ".norm1.weight"), self.f(name + ".norm1.bias"), 1e-5, 1)
-            h1 = self.conv(g1, w1, (b, h, w_, cout), bias=self.f(name + ".conv1.bias"),
-                           rowvec=self.temb_rows[:, off:off + cout], gn_stats=True, fuse_gn=self._gn_of(name + ".norm2", 1e-5, 1))
-            self.pool.put(g1)
+        h1 = self._norm_conv(name, 1, x, skip, cout, rowvec=self.temb_rows[:, off:off + cout],
+                             fuse_gn=self._gn_of(name + ".norm2", 1e-5, 1))
         if cin != cout:
             res = self.conv(x, self.w(name + ".conv_shortcut.weight"), (b, h, w_, cout), x2=skip,
                             bias=self.f(name + ".conv_shortcut.bias"), taps=1, pad=0)
         else:
             assert skip is None
             res = x
-        w2 = self.w(name + ".conv2.weight")
-        p2 = self.gn_in_conv_ok(h1, None, w2, (b, h, w_, cout), res)
-        if p2 is not None:           # norm2 + SiLU inside conv2
-            out = self.conv(h1, w2, (b, h, w_, cout), bias=self.f(name + ".conv2.bias"), residual=res, gn_stats=True, fuse_gn=next_gn,
-                            gn_in=(p2[0], p2[1], self.f(name + ".norm2.weight"), self.f(name + ".norm2.bias"), 1e-5, 1))
-            self.pool.put(h1)
-        else:
-            g2 = self.gn(h1, None, self.f(name + ".norm2.weight"), self.f(name + ".norm2.bias"), 1e-5, 1)
-            self.pool.put(h1)
-            out = self.conv(g2, w2, (b, h, w_, cout), bias=self.f(name + ".conv2.bias"), residual=res, gn_stats=True, fuse_gn=next_gn)
-            self.pool.put(g2)
+        out = self._norm_conv(name, 2, h1, None, cout, release_x=True, residual=res, fuse_gn=next_gn)
         if res is not x:
             self.pool.put(res)
         return out
@@ -666,16 +709,26 @@ class UNetPlan(_Plan):
             if geglu:               # row order of the fused GEGLU epilogue; c1 / bias follow their rows
                 idx = geglu_interleave(torch.arange(w16.shape[0])[:, None].float(), torch.zeros(w16.shape[0]))[0][:, 0].long()
                 w16, c1, bias = w16[idx], c1[idx], bias[idx]
-            return self.dev(w16.contiguous()), self.dev(c1.contiguous()), self.dev(bias.contiguous())
-        t = self.cached((u + tb, "lnfold", name), make)
-        if self.wcache is not None:
-            self.keep += list(t)
-        return t
+            return tuple(self.be.to_device(t.contiguous()) for t in (w16, c1, bias))
+        return self.cached((u + tb, "lnfold", name), make)
+
+    def _ln_then_linear(self, x, out_shape, fold, folded, plain, ln, flags=0):
+        """The linear that consumes a LayerNorm of ``x``: folded into the GEMM where the policy says so (``fold``: row
+        statistics in the GEMM's own K loop) or the producer of ``x`` left row partials (``ln_partials``), else a LayerNorm
+        launch (``ln()`` returns the normalised copy) and the plain linear.  ``folded()`` gives (w, c1, bias) as
+        ``_ln_linear`` does, ``plain()`` gives (w, bias)."""
+        st = self.ln_partials.get(x.data_ptr())
+        if fold or st is not None:
+            w, c1, bias = folded()
+            return self.conv(x, w, out_shape, bias=bias, taps=1, pad=0, flags=flags, ln_c1=c1,
+                             ln_stats_in=None if fold else st)
+        w, bias = plain()
+        return self.conv(ln(), w, out_shape, bias=bias, taps=1, pad=0, flags=flags)
 
     def _transformer(self, site, x):
         b, h, w_, c = x.shape
         shp = (b, h, w_, c)
-        tb = site + ".transformer_blocks.0"
+        u, tb = self.prefix, site + ".transformer_blocks.0"
         m_rows = b * h * w_
         fold1, fold2, fold3 = (fold_here(m_rows, 3 * c, c), fold_here(m_rows, c, c) and site not in self.a2,
                                fold_here(m_rows, 8 * c, c, True))
@@ -685,24 +738,7 @@ class UNetPlan(_Plan):
         fused_head = (rowblock and FUSED_HEAD and c == 320 and (h * w_) % 64 == 0 and m_rows // 64 >= FFN_MIN_BLOCKS
                       and xpart is not None and xpart[1] <= 256)
         ext = LN_STATS_FROM_PRODUCER and LN_FOLD == "auto"
-        if fused_head:               # norm -> proj_in -> norm1 -> q|k|v in one launch (csrc/tf_head.hip)
-            u = self.prefix
-
-            def _head():
-                return self.dev(pack_head_stream(self.sd[u + site + ".proj_in.weight"], *[self.sd[u + tb + f".attn1.to_{n}.weight"] for n in "qkv"]))
-            hstream = self.cached((self.prefix + tb, "head_stream"), _head)
-            if self.wcache is not None:
-                self.keep.append(hstream)
-            hs = self.pool.get(shp)
-            qkv = self.pool.get((b, h, w_, 3 * c))
-            self.rec(self.be.tf_head, x.view(b, h * w_, c), hstream, xpart[0], xpart[1], self.f(site + ".norm.weight"),
-                     self.f(site + ".norm.bias"), self.f(site + ".proj_in.bias"), self.f(tb + ".norm1.weight"),
-                     self.f(tb + ".norm1.bias"), hs.view(b, h * w_, c), qkv.view(b, h * w_, 3 * c))
-        else:
-            g = self.gn(x, None, self.f(site + ".norm.weight"), self.f(site + ".norm.bias"), 1e-6, 0)
-            hs = self.conv(g, self.w(site + ".proj_in.weight"), shp, bias=self.f(site + ".proj_in.bias"),
-                           taps=1, pad=0, ln_stats=LN_STATS_FROM_PRODUCER and LN_FOLD == "auto" and not fold1)
-            self.pool.put(g)
+        qkv_keys = [f".attn1.to_{n}.weight" for n in "qkv"]
         ln_box = [None]                 # the normalised copy, allocated only if some LayerNorm still runs as a kernel
 
         def ln_of(src, norm):
@@ -711,28 +747,33 @@ class UNetPlan(_Plan):
             self.rec(self.be.layernorm, src, self.f(tb + norm + ".weight"), self.f(tb + norm + ".bias"), ln_box[0])
             return ln_box[0]
         # attn1 (self)
-        st1 = self.ln_partials.get(hs.data_ptr())
-        if fused_head:
-            pass
-        elif fold1 or st1 is not None:
-            wqkv, c1, bqkv = self._ln_linear(tb, ".norm1", "qkv", [f".attn1.to_{n}.weight" for n in "qkv"])
-            qkv = self.conv(hs, wqkv, (b, h, w_, 3 * c), bias=bqkv, taps=1, pad=0, ln_c1=c1,
-                            ln_stats_in=None if fold1 else st1)
+        if fused_head:               # norm -> proj_in -> norm1 -> q|k|v in one launch (csrc/tf_head.hip)
+            hstream = self.cached((u + tb, "head_stream"), lambda: self.be.to_device(pack_head_stream(
+                self.sd[u + site + ".proj_in.weight"], *[self.sd[u + tb + k] for k in qkv_keys])))
+            hs = self.pool.get(shp)
+            qkv = self.pool.get((b, h, w_, 3 * c))
+            self.rec(self.be.tf_head, x.view(b, h * w_, c), hstream, xpart[0], xpart[1], self.f(site + ".norm.weight"),
+                     self.f(site + ".norm.bias"), self.f(site + ".proj_in.bias"), self.f(tb + ".norm1.weight"),
+                     self.f(tb + ".norm1.bias"), hs.view(b, h * w_, c), qkv.view(b, h * w_, 3 * c))
         else:
-            wqkv = self.cached((self.prefix + tb, "qkv"), lambda: self.dev(
-                torch.cat([self.sd[self.prefix + tb + f".attn1.to_{n}.weight"] for n in "qkv"]), self.dtype))
-            qkv = self.conv(ln_of(hs, ".norm1"), wqkv, (b, h, w_, 3 * c), taps=1, pad=0)
+            g = self.gn(x, None, self.f(site + ".norm.weight"), self.f(site + ".norm.bias"), 1e-6, 0)
+            hs = self.conv(g, self.w(site + ".proj_in.weight"), shp, bias=self.f(site + ".proj_in.bias"),
+                           taps=1, pad=0, ln_stats=ext and not fold1)
+            self.pool.put(g)
+
+            def _qkv():
+                return self.be.to_device(torch.cat([self.sd[u + tb + k] for k in qkv_keys]), self.dtype)
+            qkv = self._ln_then_linear(hs, (b, h, w_, 3 * c), fold1, lambda: self._ln_linear(tb, ".norm1", "qkv", qkv_keys),
+                                       lambda: (self.cached((u + tb, "qkv"), _qkv), None), lambda: ln_of(hs, ".norm1"))
         att = self.pool.get(shp)
         self.rec(self.be.self_attn, qkv.view(b, h * w_, 3 * c), att.view(b, h * w_, c), HEADS)
         self.pool.put(qkv)
-        fused2 = site in self.a2
         h2 = self.conv(att, self.w(tb + ".attn1.to_out.0.weight"), shp,
                        bias=self.f(tb + ".attn1.to_out.0.bias"), residual=hs, taps=1, pad=0,
                        ln_stats=ext and not fold2)
         self.pool.put(hs)
-        # attn2 (DADD cross-attention)
-        st3 = None
-        if fused2:                   # one kernel: x (W_q K^T) -> 24 softmaxes -> P (V W_o^T) + bias + residual
+        # attn2 (DADD cross-attention); its output h3 comes with row partials where the GEGLU projection can fold norm3 with them
+        if site in self.a2:          # one kernel: x (W_q K^T) -> 24 softmaxes -> P (V W_o^T) + bias + residual
             st = self.a2[site]
             st2 = self.ln_partials.get(h2.data_ptr())
             kw2 = {}
@@ -744,42 +785,30 @@ class UNetPlan(_Plan):
                 lnx = ln_of(h2, ".norm2")
             h3 = self.pool.get(shp)
             if ext and not fold3 and c % 80 == 0 and not fused_tail:
-                st3 = self.be.zeros((c // 80, m_rows, 2), F32)
-                self.keep.append(st3)
-                kw2["ln_stats_out"] = st3
+                kw2["ln_stats_out"] = self._ln_partials_for(h3, c // 80)
             self.rec(self.be.attn2_fused, lnx.view(b, h * w_, c), st["mcat"], st["vw"],
                      self.f(tb + ".attn2.to_out.0.bias"), h2.view(b, h * w_, c), h3.view(b, h * w_, c), **kw2)
         else:
-            st2 = self.ln_partials.get(h2.data_ptr())
-            if fold2 or st2 is not None:
-                wq, c1, bq = self._ln_linear(tb, ".norm2", "to_q", [".attn2.to_q.weight"])
-                q = self.conv(h2, wq, shp, bias=bq, taps=1, pad=0, ln_c1=c1, ln_stats_in=None if fold2 else st2)
-            else:
-                q = self.conv(ln_of(h2, ".norm2"), self.w(tb + ".attn2.to_q.weight"), shp, taps=1, pad=0)
+            q = self._ln_then_linear(
+                h2, shp, fold2, lambda: self._ln_linear(tb, ".norm2", "to_q", [".attn2.to_q.weight"]),
+                lambda: (self.w(tb + ".attn2.to_q.weight"), None), lambda: ln_of(h2, ".norm2"))
             self.rec(self._xattn, site, q.view(b, h * w_, c), att.view(b, h * w_, c))
             self.pool.put(q)
             h3 = self.conv(att, self.w(tb + ".attn2.to_out.0.weight"), shp,
                            bias=self.f(tb + ".attn2.to_out.0.bias"), residual=h2, taps=1, pad=0,
                            ln_stats=ext and not fold3 and not fused_tail)
-            st3 = self.ln_partials.get(h3.data_ptr())
         self.pool.put(h2, att)
         if fused_tail:               # norm3 -> GEGLU -> FF-out + h3 -> proj_out + x in one launch (csrc/ffn_block.hip)
             def _tail():
-                u = self.prefix
                 st, b1p = pack_ffn_stream(self.sd[u + tb + ".ff.net.0.proj.weight"], self.sd[u + tb + ".ff.net.0.proj.bias"],
                                           self.sd[u + tb + ".ff.net.2.weight"], self.sd[u + site + ".proj_out.weight"])
-                return self.dev(st), self.dev(b1p)
-            stream, b1p = self.cached((self.prefix + tb, "ffn_stream"), _tail)
-            if self.wcache is not None:
-                self.keep += [stream, b1p]
+                return self.be.to_device(st), self.be.to_device(b1p)
+            stream, b1p = self.cached((u + tb, "ffn_stream"), _tail)
             out = self.pool.get(shp)
             nchunk = (h * w_) // 32
             gkw = {}
             if GN_FROM_EPILOGUE and nchunk <= 128 and (h * w_) * (c // 32) * 2 > GN_FUSED_MAX_BYTES:
-                ws = self.be.zeros((b * nchunk * GROUPS * 2,), F32)
-                self.keep.append(ws)
-                self.gn_partials[out.data_ptr()] = (ws, nchunk)
-                gkw = dict(gn_ws=ws, gn_nchunk=nchunk)
+                gkw = self._gn_partials_for(out, nchunk)
             if ln_box[0] is not None:
                 self.pool.put(ln_box[0])
             self.rec(self.be.ffn_block, h3.view(b, h * w_, c), stream, self.f(tb + ".norm3.weight"), self.f(tb + ".norm3.bias"),
@@ -787,22 +816,16 @@ class UNetPlan(_Plan):
                      out.view(b, h * w_, c), **gkw)
             self.pool.put(h3)
             return out
+
+        def _geglu():
+            wf, bf = geglu_interleave(self.sd[u + tb + ".ff.net.0.proj.weight"], self.sd[u + tb + ".ff.net.0.proj.bias"])
+            return self.be.to_device(wf, self.dtype), self.be.to_device(bf.float())
         # GEGLU feed-forward
-        if fold3 or st3 is not None:
-            wf, c1, bf = self._ln_linear(tb, ".norm3", "geglu", [".ff.net.0.proj.weight"], ".ff.net.0.proj.bias", geglu=True)
-            ff = self.conv(h3, wf, (b, h, w_, 4 * c), bias=bf, taps=1, pad=0, flags=L.EPI_GEGLU, ln_c1=c1,
-                           ln_stats_in=None if fold3 else st3)
-        else:
-            def _geglu():
-                wf, bf = geglu_interleave(self.sd[self.prefix + tb + ".ff.net.0.proj.weight"],
-                                          self.sd[self.prefix + tb + ".ff.net.0.proj.bias"])
-                return self.dev(wf, self.dtype), self.dev(bf.float())
-            wf, bf = self.cached((self.prefix + tb, "geglu"), _geglu)
-            if self.wcache is not None:
-                self.keep += [wf, bf]
-            ff = self.conv(ln_of(h3, ".norm3"), wf, (b, h, w_, 4 * c), bias=bf, taps=1, pad=0, flags=L.EPI_GEGLU)
-        ln = ln_box[0]
-        self.pool.put(ln)
+        ff = self._ln_then_linear(
+            h3, (b, h, w_, 4 * c), fold3,
+            lambda: self._ln_linear(tb, ".norm3", "geglu", [".ff.net.0.proj.weight"], ".ff.net.0.proj.bias", geglu=True),
+            lambda: self.cached((u + tb, "geglu"), _geglu), lambda: ln_of(h3, ".norm3"), flags=L.EPI_GEGLU)
+        self.pool.put(ln_box[0])
         h4 = self.conv(ff, self.w(tb + ".ff.net.2.weight"), shp, bias=self.f(tb + ".ff.net.2.bias"),
                        residual=h3, taps=1, pad=0)
         self.pool.put(ff, h3)
@@ -830,11 +853,7 @@ class UNetPlan(_Plan):
         if GN_FROM_EPILOGUE and (s * s) % 256 == 0 and (s * s) // 256 <= 128 and s * s * 10 * 2 > GN_FUSED_MAX_BYTES:
             # conv_in writes the GroupNorm chunk partials of its output (256 pixels per chunk): no statistics pass for the
             # first ResNet's norm1 nor for the last up block's skip-concat, and both can normalise inside their 3x3 conv
-            nchunk = (s * s) // 256
-            ws = self.be.zeros((b * nchunk * GROUPS * 2,), F32)
-            self.keep.append(ws)
-            self.gn_partials[h.data_ptr()] = (ws, nchunk)
-            gkw = dict(gn_ws=ws, gn_nchunk=nchunk)
+            gkw = self._gn_partials_for(h, (s * s) // 256)
         self.rec(self.be.conv_in_nchw, self.lat_in, self.w("conv_in.weight", pack_conv_cin8), self.f("conv_in.bias"), h, **gkw)
         skips = [h]
         for i in range(4):
@@ -886,32 +905,7 @@ class UNetPlan(_Plan):
         g = self.gn(h, None, self.f("conv_norm_out.weight"), self.f("conv_norm_out.bias"), 1e-5, 1)
         self.rec(self._emit_eps, g, self.w("conv_out.weight", pack_conv_cout4), self.f("conv_out.bias"))
         self.pool.put(h, g)
-        assert not self.gn_ready, "a GroupNorm written by a finish kernel was never consumed"
-        self._insert_weight_prefetch()
-
-    def _insert_weight_prefetch(self):
-        """Every layer's weights are cold when its kernel starts (1.76 GB per step against 256 MB of Infinity Cache).  A
-        launch whose weights are at least WEIGHT_PREFETCH_MIN_BYTES gets a ``be.prefetch`` of them WEIGHT_PREFETCH_AHEAD
-        weight-bearing launches earlier - a side branch of the captured graph (``dadd_prefetch``) - and the plan ends with
-        the join.  Reads only: results are unchanged."""
-        if not WEIGHT_PREFETCH_AHEAD:
-            return
-        wops = []                       # (op index, weight tensor) of the launches that stream a weight operand
-        for i, (fn, a, k) in enumerate(self.ops):
-            name = getattr(fn, "__name__", "")
-            if name == "igemm":
-                wops.append((i, a[1]))
-            elif name in ("ffn_block", "tf_head"):
-                wops.append((i, a[1]))
-        inserts = []
-        for j, (i, w) in enumerate(wops):
-            if w.numel() * w.element_size() < WEIGHT_PREFETCH_MIN_BYTES or j < WEIGHT_PREFETCH_AHEAD:
-                continue
-            inserts.append((wops[j - WEIGHT_PREFETCH_AHEAD][0], w))
-        for at, w in sorted(inserts, key=lambda t: -t[0]):       # back to front: earlier indices stay valid
-            self.ops.insert(at, (self.be.prefetch, (w,), {}))
-        if inserts:
-            self.ops.append((self.be.prefetch_join, (), {}))
+        self._end_build(prefetch_weights=True)
 
     # -- step-invariant preparation ----------------------------------------------------------------
     def set_cond(self, cond: torch.Tensor, slot: int = 0):
@@ -1002,23 +996,14 @@ class UNetPlan(_Plan):
         return self.be.clone(self.eps_out[0])
 
 
-# ----------------------------------------------------------------------------- VAE decoder
-class VaeDecoderPlan(_Plan):
-    def __init__(self, be, sd, batch: int, side: int, *, prefix="vae.vae", latent_scale=0.18215):
-        super().__init__(be)
+# ----------------------------------------------------------------------------- VAE
+class _VaePlan(_Plan):
+    """What the decoder and the encoder plans share: fp16 storage, the ResNet and the attention block."""
+
+    def __init__(self, be, sd, batch: int, side: int, prefix):
+        super().__init__(be, sd=sd, prefix=prefix)
         self.B, self.S = batch, side
-        self.sd, self.prefix = sd, prefix + "."
         self.gn_ws = be.empty((batch * L.GN_MAX_CHUNKS * GROUPS * 2,), F32)
-        self.z_in = be.zeros((batch, 4, side, side), F32)
-        self.img_out = be.zeros((batch, 3, side * 8, side * 8), F32)
-        self.inv_scale = 1.0 / latent_scale
-        self._build()
-
-    def w(self, key, pack=pack_conv):
-        return self.dev(pack(self.sd[self.prefix + key]))
-
-    def f(self, key):
-        return self.dev(self.sd[self.prefix + key].float())
 
     def _res(self, name, x):
         b, h, w_, cin = x.shape
@@ -1055,6 +1040,24 @@ class VaeDecoderPlan(_Plan):
         self.pool.put(att)
         return out
 
+    def _mid(self, side, h):
+        """ResNet, attention, ResNet of ``side`` ("decoder." / "encoder."); ``h`` returns to the pool."""
+        for blk, name in ((self._res, "resnets.0"), (self._attn, "attentions.0"), (self._res, "resnets.1")):
+            hn = blk(f"{side}mid_block.{name}", h)
+            self.pool.put(h)
+            h = hn
+        return h
+
+
+# ----------------------------------------------------------------------------- VAE decoder
+class VaeDecoderPlan(_VaePlan):
+    def __init__(self, be, sd, batch: int, side: int, *, prefix="vae.vae", latent_scale=0.18215):
+        super().__init__(be, sd, batch, side, prefix)
+        self.z_in = be.zeros((batch, 4, side, side), F32)
+        self.img_out = be.zeros((batch, 3, side * 8, side * 8), F32)
+        self.inv_scale = 1.0 / latent_scale
+        self._build()
+
     def _build(self):
         b, s = self.B, self.S
         d = "decoder."
@@ -1064,12 +1067,7 @@ class VaeDecoderPlan(_Plan):
         self.rec(self.be.pack_latents, self.z_in, z8, self.inv_scale, pq_w, pq_b)
         h = self.pool.get((b, s, s, 512))
         self.rec(self.be.conv_cin8, z8, self.w(d + "conv_in.weight", pack_conv_cin8), self.f(d + "conv_in.bias"), h)
-        for blk in (lambda x: self._res(d + "mid_block.resnets.0", x),
-                    lambda x: self._attn(d + "mid_block.attentions.0", x),
-                    lambda x: self._res(d + "mid_block.resnets.1", x)):
-            hn = blk(h)
-            self.pool.put(h)
-            h = hn
+        h = self._mid(d, h)
         for i in range(4):
             for j in range(3):
                 hn = self._res(d + f"up_blocks.{i}.resnets.{j}", h)
@@ -1086,10 +1084,11 @@ class VaeDecoderPlan(_Plan):
         self.rec(self.be.conv_cout4, g, self.w(d + "conv_out.weight", pack_conv_cout4),
                  self.f(d + "conv_out.bias"), self.img_out, 1)
         self.pool.put(h, g)
+        self._end_build()
 
 
 # ----------------------------------------------------------------------------- VAE encoder
-class VaeEncoderPlan(VaeDecoderPlan):
+class VaeEncoderPlan(_VaePlan):
     """``SDVAE.encode`` (src/models/vae/vae.py:71-88) -> diffusers ``AutoencoderKL.encode``: images (B,3,H,W) in
     [-1,1] -> moments (mean, logvar), each (B,4,H/8,W/8) fp32 NCHW.  Same kernels as the decoder; the three
     downsamplers are 3x3 / stride-2 convolutions with the asymmetric (0,1,0,1) padding folded into the gather
@@ -1097,11 +1096,8 @@ class VaeEncoderPlan(VaeDecoderPlan):
     ``quant_conv`` (1x1, 8 -> 8) is composed into ``conv_out`` at plan time (two linear maps: exact algebra, one
     rounding of the composed weights to fp16).  ``side`` is the LATENT side (image side / 8)."""
 
-    def __init__(self, be, sd, batch: int, side: int, *, prefix="vae.vae", wcache=None):
-        _Plan.__init__(self, be, wcache)
-        self.B, self.S = batch, side
-        self.sd, self.prefix = sd, prefix + "."
-        self.gn_ws = be.empty((batch * L.GN_MAX_CHUNKS * GROUPS * 2,), F32)
+    def __init__(self, be, sd, batch: int, side: int, *, prefix="vae.vae"):
+        super().__init__(be, sd, batch, side, prefix)
         self.img_in = be.zeros((batch, 3, side * 8, side * 8), F32)
         self.mean = be.zeros((batch, 4, side, side), F32)
         self.logvar = be.zeros((batch, 4, side, side), F32)
@@ -1128,12 +1124,7 @@ class VaeEncoderPlan(VaeDecoderPlan):
                                gn_stats=True)
                 self.pool.put(h)
                 h = hn
-        for blk in (lambda x: self._res(e + "mid_block.resnets.0", x),
-                    lambda x: self._attn(e + "mid_block.attentions.0", x),
-                    lambda x: self._res(e + "mid_block.resnets.1", x)):
-            hn = blk(h)
-            self.pool.put(h)
-            h = hn
+        h = self._mid(e, h)
         g = self.gn(h, None, self.f(e + "conv_norm_out.weight"), self.f(e + "conv_norm_out.bias"), 1e-6, 1)
         # moments = quant_conv(conv_out(g)):  W' = Q W,  b' = Q b + q   (Q: 8x8 of the 1x1 conv)
         u = self.prefix
@@ -1144,6 +1135,7 @@ class VaeEncoderPlan(VaeDecoderPlan):
         self.rec(self.be.conv_cout4, g, self.dev(pack_conv_cout4(wq[:4])), self.dev(bq[:4].contiguous()), self.mean, 0)
         self.rec(self.be.conv_cout4, g, self.dev(pack_conv_cout4(wq[4:])), self.dev(bq[4:].contiguous()), self.logvar, 2)
         self.pool.put(h, g)
+        self._end_build()
 
 
 # ----------------------------------------------------------------------------- DDIM loop

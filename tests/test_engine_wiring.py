@@ -465,3 +465,69 @@ def test_groupnorm_statistics_from_the_producing_epilogue(monkeypatch):
     monkeypatch.setitem(E.TILING_OVERRIDE, E.tiling_key(b * hw * hw, cout, cin, 1, False, False), (64, 64, 1, 0))
     out3 = plan.conv(x, w1, (b, hw, hw, cout), taps=1, pad=0, gn_stats=True)
     assert out3.data_ptr() not in plan.gn_partials
+
+
+def _fuse_gn_case(monkeypatch, b=1):
+    """A 16 x 16 x 320 conv planned with two K slices: its finish kernel also writes the GroupNorm named by ``fuse_gn``
+    (split-K > 1, n % 64 == 0, a (sample, group) slab of 5 KiB <= GN_FUSED_MAX_BYTES)."""
+    g = torch.Generator().manual_seed(5)
+    cin, cout, hw = 64, 320, 16
+    x = torch.randn(b, hw, hw, cin, generator=g).to(torch.float16)
+    w = (torch.randn(cout, 9 * cin, generator=g) / 24).to(torch.float16)
+    hint = (1 + 0.1 * torch.randn(cout, generator=g), 0.1 * torch.randn(cout, generator=g), 1e-5, 1)
+    monkeypatch.setitem(E.TILING_OVERRIDE, E.tiling_key(b * hw * hw, cout, 9 * cin, 9, False, False), (128, 160, 2, 0))
+    return x, w, (b, hw, hw, cout), hint
+
+
+def test_a_normalised_copy_nobody_consumes_fails_the_build(full_sd, monkeypatch):
+    """``conv(fuse_gn=...)`` leaves the GroupNorm of its output in ``gn_ready`` for the consuming ``gn()``.  A plan that
+    recycles the output, or ends its build, without that ``gn()`` has lost a pool buffer: an error for every plan family."""
+    x, w, shape, hint = _fuse_gn_case(monkeypatch)
+    plan = E._Plan(TorchRefBackend())
+    out = plan.conv(x, w, shape, fuse_gn=hint)
+    assert out.data_ptr() in plan.gn_ready
+    with pytest.raises(AssertionError, match="never consumed"):
+        plan._end_build()
+    with pytest.raises(AssertionError, match="never consumed"):
+        plan.pool.put(out)
+    y = plan.gn(out, None, *hint)                        # the consumer takes the copy: no launch, and the ledger is settled
+    assert y is plan.ops[-1][2]["gn_apply"][0] and len(plan.ops) == 1 and not plan.gn_ready
+    plan.pool.put(out, y)
+    plan._end_build()
+
+    class Leaky(E.VaeDecoderPlan):
+        def _build(self):
+            self.conv(x, w, shape, fuse_gn=hint)
+            super()._build()
+    with pytest.raises(AssertionError, match="never consumed"):
+        Leaky(TorchRefBackend(), full_sd, 1, 8)
+    with pytest.raises(AssertionError, match="never consumed"):
+        class LeakyUNet(E.UNetPlan):
+            def _build(self):
+                self.conv(x, w, shape, fuse_gn=hint)
+                super()._build()
+        LeakyUNet(TorchRefBackend(), full_sd, 1, 8)
+
+
+def test_plans_keep_each_device_tensor_once(full_sd, monkeypatch):
+    """``plan.keep`` (what ``parameters()`` of the modules iterates) holds tensors only and none twice: without a weight
+    cache, on a cache miss (first plan) and on a cache hit (second plan), with every packing routine in use."""
+    monkeypatch.setattr(E, "FFN_MIN_BLOCKS", 1)
+    cache = {}
+    miss = E.UNetPlan(TorchRefBackend(), full_sd, 1, 16, wcache=cache)
+    n_miss = len(cache)
+    hit = E.UNetPlan(TorchRefBackend(), full_sd, 2, 16, wcache=cache)
+    assert any(isinstance(v, tuple) for v in cache.values())            # (folded LayerNorm, ffn stream: several tensors per key)
+    assert hit.w("conv_in.weight", E.pack_conv_cin8) is miss.w("conv_in.weight", E.pack_conv_cin8)
+    monkeypatch.setattr(E, "LN_FOLD", False)                            # ... and the unfolded qkv / GEGLU weights
+    plain = E.UNetPlan(TorchRefBackend(), full_sd, 1, 16, wcache=cache)
+    assert len(cache) > n_miss
+    plans = {"miss": miss, "hit": hit, "plain": plain, "no cache": E.UNetPlan(TorchRefBackend(), full_sd, 2, 8),
+             "vae": E.VaeDecoderPlan(TorchRefBackend(), full_sd, 1, 8)}
+    for name, plan in plans.items():
+        assert all(isinstance(t, torch.Tensor) for t in plan.keep), name
+        assert len({id(t) for t in plan.keep}) == len(plan.keep), name
+        held = {id(t) for t in plan.keep}
+        for fn, a, k in plan.ops:                        # every weight-like operand of a recorded igemm is kept alive
+            if getattr(fn, "__name__", "") == "igemm":
+                assert id(a[1]) in held, name
