@@ -337,7 +337,9 @@ __global__ __launch_bounds__(NW * 64, DR <= 96 ? 2 : 1) void flash_kernel(const 
 #pragma unroll
       for (int f = 0; f < QF; ++f) {
         const float dlt = (kt == 0 || mc[f] > 8.0f) ? mc[f] : 0.f;    // this column's reference moves by dlt (0: it stays)
-        const float alpha = __builtin_amdgcn_exp2f(-dlt);
+        // tile 0 has nothing to rescale (O and the row sum are still 0), and its dlt is the tile's maximum itself: below -128
+        // exp2(-dlt) is +inf and 0 * inf would poison the row with NaN.  kt == 0 is wave-uniform.
+        const float alpha = kt == 0 ? 1.0f : __builtin_amdgcn_exp2f(-dlt);
         negm[f] -= dlt;
         if (!SUMCOL) lrow[f] *= alpha;
 #pragma unroll

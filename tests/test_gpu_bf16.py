@@ -253,7 +253,9 @@ def test_layernorm_bf16(hip, m, c):
 @pytest.mark.parametrize("d", [40, 80, 160])
 @pytest.mark.parametrize("n", [576, 144, 36, 9, 4096])
 def test_self_attention_bf16(hip, d, n):
-    """flash_kernel_bf16: ragged key counts of the 24x24 latent (576 / 144 / 36 / 9) and the 8-wave d = 40 variant."""
+    """flash_kernel_bf16: ragged key counts of the 24x24 latent (576 / 144 / 36 / 9) and n = 4096.  At b = 2 the latter
+    still runs the four-wave d = 40 kernel (2 * 8 * 16 = 256 < 512 workgroups); the eight-wave variant is compared in
+    tests/test_gpu_attention_edges.py."""
     heads, b = 8, 2
     c = heads * d
     qkv = rnd((b, n, 3 * c), 30)
