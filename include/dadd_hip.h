@@ -339,6 +339,36 @@ int dadd_tri_xattn_bf16(const void* q, const void* kv, void* out, const float* g
                         const float* lambda_dev, int mode, int B, int N, int heads, int d, int T, int ld_kv,
                         void* stream);
 
+/* ---- weight gradient of the implicit-GEMM convolution / linear (training backward) --------------
+ * dW[n][tap][c] = sum_m dy[m][n] * x[b, oy*stride+ky-pad, ox*stride+kx-pad, c],  db[n] = sum_m dy[m][n],
+ * m = (b*Ho+oy)*Wo+ox over ALL rows: a GEMM that reduces over the row index, fp32 accumulation, fp32 results in the
+ * library's weight layout [N][taps][Ctot].  The gather is the forward's (dadd_conv_igemm_f16): `ups` = 1 reads x through
+ * the nearest 2x upsample, pixels outside the map are zero.  The data gradient needs no entry point of its own: for
+ * stride 1 it is dadd_conv_igemm_f16 on dy with the weight re-laid as wt[c][8-tap][n].
+ * Stands behind the weight / bias gradients that loss.backward() of DiffusionModuleWithIP.training_step
+ * (src/models/diffusion_module_ip.py:392-462) produces for the nn.Linear / nn.Conv2d modules under OrdinalUNet.forward
+ * (src/models/unet/unet.py:140-144).
+ * Contract (DADD_EINVAL and no launch otherwise): C % 64 == 0, N % 8 == 0, every ld_* a multiple of 8, 16-byte aligned
+ * pointers, 1 <= splitm <= ceil(M/32) (a slice is a whole number of 32-row MFMA steps); taps = 1 with pad 0 (stride 1, Ho x Wo == Hi x Wi), or taps = 9 with pad 1 and
+ * stride 1 or 2, or ups = 1 (stride 1); M = B*Ho*Wo is arbitrary.
+ * splitm > 1 splits the reduction over splitm workgroups per output tile; each writes an fp32 slab into `partial` and a
+ * finish kernel launched by the same call adds the slabs in slice order (no floating-point atomics: results are
+ * bit-reproducible).  A skip-concat input [x | x2] is two calls, the second with dw advanced by C1, both with
+ * ld_tap = C1 + C2: a call touches only the columns of its own source. */
+typedef struct {
+  const void* dy;    /* [B][Ho][Wo][N] 16-bit, ld_dy elements between pixels (a column slice of a wider tensor is allowed) */
+  const void* x;     /* [B][Hi][Wi][C] 16-bit, ld_x elements between pixels (likewise) */
+  float* dw;         /* fp32, element (n,tap,c) at dw[n*ld_dw + tap*ld_tap + c]; overwritten, not accumulated */
+  float* dbias;      /* N floats or NULL */
+  float* partial;    /* splitm > 1: fp32 scratch, splitm*(N*taps*C + N) floats */
+  int32_t B, Hi, Wi, C, Ho, Wo, N;
+  int32_t taps, stride, ups, pad;
+  int32_t ld_dy, ld_x, ld_dw, ld_tap;
+  int32_t splitm;    /* >= 1, chosen by the caller */
+} dadd_wgrad_desc;
+int dadd_conv_wgrad_f16(const dadd_wgrad_desc* d, void* stream);
+/* the bf16 sibling (same descriptor and contract, bf16 dy / x) is declared in dadd_hip_grad.h */
+
 /* ---- hipGraph capture of the step loop ----------------------------------------------------- */
 int dadd_graph_begin(void* stream);
 int dadd_graph_end(void* stream, void** graph_exec_out);

@@ -48,6 +48,8 @@ class HipBackend:
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self._desc = L.IgemmDesc()
+        self._wdesc = L.WgradDesc()
+        self._n_cu = None
         self._capturing = False     # between graph_begin() and graph_end(): no cross-stream waits may be recorded
         self._prof_on = False
         with torch.cuda.device(self.device):
@@ -233,6 +235,88 @@ class HipBackend:
         if partial is not None:
             assert partial.numel() >= splitk * b * ho * wo * n
         L.check(fn(C.byref(d), self.s))
+
+    # -- training backward of the matrix products (csrc/wgrad.hip; the data gradient is the forward kernel)
+    def wgrad_splitm(self, m, n, c, taps=1):
+        """Default number of reduction slices of ``wgrad``: the output has ceil(N/64) * taps * C/64 tiles of 64 x 64,
+        usually far fewer than the device has CUs, and a reduction of M rows behind each; split it until the launch has
+        about 2 workgroups per CU, every slice keeping at least 64 rows (the kernel itself takes slices down to one 32-row
+        MFMA step, ``splitm <= ceil(M/32)``)."""
+        if self._n_cu is None:
+            self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        tiles = -(-n // 64) * taps * (c // 64)
+        return max(1, min(-(-2 * self._n_cu // tiles), -(-m // 64)))
+
+    @staticmethod
+    def wgrad_partial_numel(splitm, n, c, taps=1):
+        """fp32 elements of the ``partial`` scratch of a ``wgrad`` call (nothing for ``splitm == 1``)."""
+        return splitm * (n * taps * c + n) if splitm > 1 else 0
+
+    @staticmethod
+    def _pixel_ld(t):
+        """Elements between two pixels of an NHWC / token-major tensor whose rows may be a column slice of a wider one."""
+        ld = t.stride(-2)
+        want, ok = ld, t.stride(-1) == 1
+        for size, st in zip(reversed(t.shape[:-1]), reversed(t.stride()[:-1])):
+            ok = ok and (size == 1 or st == want)
+            want *= size
+        if not ok:
+            raise ValueError(f"expected dense pixels with one row stride, got shape {tuple(t.shape)} strides {t.stride()}")
+        return ld
+
+    def wgrad(self, dy, x, dw, *, dbias=None, taps=1, stride=1, ups=0, pad=0, splitm=None, partial=None, ld_tap=None):
+        """Weight (and bias) gradient of ``igemm``: dw[n][tap][c] = sum_m dy[m][n] * x[gather(m, tap)][c] and
+        dbias[n] = sum_m dy[m][n], fp32, overwritten.  dy [B,Ho,Wo,N] and x [B,Hi,Wi,C] (or [M,N] and [M,C] for a linear)
+        are fp16 or bf16 and may be channel slices of wider tensors: the row strides travel.  dw is fp32 [N,taps,C] or
+        [N,taps*C], possibly a column view of a wider weight gradient (skip-concat: one call per source into the
+        [..., :C1] and [..., C1:] views of one [N,taps,C1+C2] tensor); for the 2-D form ``ld_tap`` gives the elements
+        between taps (default C).
+        ``splitm`` = number of slices of the M reduction; ``None`` takes ``wgrad_splitm``: enough slices for about two
+        workgroups per CU, at least 64 rows per slice.  ``splitm > 1`` needs ``partial``, fp32 with
+        ``wgrad_partial_numel`` = splitm * (N*taps*C + N) elements; the slabs are added in slice order, so the result is
+        bit-reproducible."""
+        if dy.dim() == 2:
+            dy, x = dy.unsqueeze(0).unsqueeze(0), x.unsqueeze(0).unsqueeze(0)
+        b, ho, wo, n = dy.shape
+        bx, hi, wi, c = x.shape
+        assert bx == b and dy.dim() == 4 and x.dim() == 4
+        fn = getattr(self.lib, "dadd_conv_wgrad_" + _sfx(dy, x))
+        assert dw.dtype == torch.float32 and dw.stride(-1) == 1 and dw.shape[0] == n
+        if dw.dim() == 3:
+            assert dw.shape[1:] == (taps, c) and ld_tap in (None, dw.stride(1))
+            ld_tap = dw.stride(1)
+        else:
+            ld_tap = c if ld_tap is None else ld_tap
+            assert dw.dim() == 2 and dw.shape[1] >= (taps - 1) * ld_tap + c
+        assert dbias is None or (dbias.dtype == torch.float32 and dbias.numel() == n and dbias.is_contiguous())
+        m = b * ho * wo
+        if splitm is None:
+            splitm = self.wgrad_splitm(m, n, c, taps)
+        if splitm > 1:
+            if partial is None:
+                raise ValueError(f"wgrad with splitm = {splitm} needs a partial buffer")
+            assert partial.dtype == torch.float32 and partial.is_contiguous() \
+                and partial.numel() >= self.wgrad_partial_numel(splitm, n, c, taps), (partial.shape, splitm, n, taps, c)
+        d = self._wdesc
+        d.dy, d.x, d.dw, d.dbias, d.partial = _p(dy), _p(x), _p(dw), _p(dbias), _p(partial)
+        d.B, d.Hi, d.Wi, d.C, d.Ho, d.Wo, d.N = b, hi, wi, c, ho, wo, n
+        d.taps, d.stride, d.ups, d.pad = taps, stride, int(ups), pad
+        d.ld_dy, d.ld_x, d.ld_dw, d.ld_tap = self._pixel_ld(dy), self._pixel_ld(x), dw.stride(0), ld_tap
+        d.splitm = splitm
+        L.check(fn(C.byref(d), self.s))
+
+    def dgrad(self, dy, wt, dx, *, taps=1):
+        """Data gradient of a stride-1 ``igemm``: the forward kernel on dy [B,H,W,N] with the re-laid weight
+        wt [C, taps*N] (``grad_ops.dgrad_weight``: taps flipped, channel roles swapped) -> dx [B,H,W,C]; [M,N] -> [M,C] for
+        a linear."""
+        if dy.dim() == 2:
+            dy, dx = dy.view(1, 1, *dy.shape), dx.view(1, 1, *dx.shape)
+        n = dy.shape[-1]
+        if n % 64 != 0:
+            raise ValueError(f"dgrad contracts over the N = {n} output channels of the forward; the GEMM kernels need "
+                             "a multiple of 64 (the 4-channel end convolutions have no data gradient here)")
+        assert taps in (1, 9) and wt.shape == (dx.shape[-1], taps * n) and dy.is_contiguous() and dx.is_contiguous()
+        self.igemm(dy, wt, dx, taps=taps, pad=1 if taps == 9 else 0)
 
     def groupnorm(self, x1, x2, gamma, beta, out, ws, groups, eps, silu, ws_chunks=0):
         """``ws_chunks`` > 0: ``ws`` holds the chunk partials written by the producing GEMM's epilogue."""

@@ -23,6 +23,8 @@
 #define conv_in_nchw_kernel conv_in_nchw_kernel_bf16
 #define conv_in_nchw_gn_kernel conv_in_nchw_gn_kernel_bf16
 #define conv_cout4_kernel conv_cout4_kernel_bf16
+#define wgrad_kernel wgrad_kernel_bf16
+#define wgrad_finish_kernel wgrad_finish_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -47,3 +49,4 @@
 #define dadd_conv_in_nchw_f16 dadd_conv_in_nchw_bf16
 #define dadd_conv3x3_cout4_f16 dadd_conv3x3_cout4_bf16
 #define dadd_conv_out_ddim_f16 dadd_conv_out_ddim_bf16
+#define dadd_conv_wgrad_f16 dadd_conv_wgrad_bf16

@@ -16,7 +16,9 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            "conditioning.hip", "api.hip",
            # bf16 twins of the UNet's generic-path kernels (csrc/bf16_names.h)
            "igemm_bf16.hip", "igemm_dma_bf16.hip", "conv_halo_bf16.hip", "norm_bf16.hip", "attention_bf16.hip",
-           "elementwise_bf16.hip")
+           "elementwise_bf16.hip",
+           # training backward: the M-reduction GEMM of the weight gradient and its bf16 twin
+           "wgrad.hip", "wgrad_bf16.hip")
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -40,6 +42,13 @@ class IgemmDesc(C.Structure):
                                                            ("gn_in_ws", vp), ("gn_in_gamma", vp), ("gn_in_beta", vp), ("gn_in_nchunk", i32), ("gn_in_eps", f32),
                                                            ("gn_in_ws2", vp), ("gn_in_nchunk2", i32),
                                                            ("gn_out", vp), ("gn_out_gamma", vp), ("gn_out_beta", vp), ("gn_out_eps", f32)]
+
+
+class WgradDesc(C.Structure):
+    """Mirror of ``dadd_wgrad_desc``."""
+    _fields_ = [(n, vp) for n in ("dy", "x", "dw", "dbias", "partial")] + \
+               [(n, i32) for n in ("B", "Hi", "Wi", "C", "Ho", "Wo", "N", "taps", "stride", "ups", "pad",
+                                   "ld_dy", "ld_x", "ld_dw", "ld_tap", "splitm")]
 
 
 # name -> (restype, argtypes); every symbol include/dadd_hip.h declares
@@ -93,6 +102,7 @@ PROTOTYPES = {
     "dadd_attn_bf16": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 8 + [vp]),
     "dadd_tri_xattn_bf16": (C.c_int, [vp, vp, vp, vp, f32, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, vp]),
+    "dadd_conv_wgrad_f16": (C.c_int, [C.POINTER(WgradDesc), vp]),
     "dadd_begin_step": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "dadd_ddim_update_f32": (C.c_int, [vp, vp, vp, f32, vp, vp, i64, vp]),
     "dadd_prefetch": (C.c_int, [vp, i64, vp]),
@@ -106,6 +116,11 @@ PROTOTYPES = {
     "dadd_prof_record": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double)]),
 }
 
+# every symbol include/dadd_hip_grad.h declares (training backward only)
+GRAD_PROTOTYPES = {
+    "dadd_conv_wgrad_bf16": (C.c_int, [C.POINTER(WgradDesc), vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -114,7 +129,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
-        [os.path.join(os.path.dirname(_HERE), "include", "dadd_hip.h")]
+        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -140,7 +155,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension is required (run __graft_entry__.build()); "
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in {**PROTOTYPES, **GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
