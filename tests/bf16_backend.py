@@ -29,7 +29,7 @@ class DtypeRefBackend(TorchRefBackend):
 
     def conv_in_nchw(self, x, w, bias, out, gn_ws=None, gn_nchunk=0):
         self._log("conv_in_nchw", w, out)
-        x8 = torch.zeros(x.shape[0], x.shape[2], x.shape[3], 8, dtype=out.dtype)
+        x8 = torch.zeros(x.shape[0], x.shape[2], x.shape[3], 8, dtype=out.dtype, device=x.device)
         self.pack_latents(x, x8)
         self.conv_cin8(x8, w, bias, out)
         if gn_ws is not None:

@@ -15,6 +15,7 @@ from tests.torch_backend import TorchRefBackend
 pytestmark = pytest.mark.gpu
 
 F16, F32 = torch.float16, torch.float32
+DEV = torch.device("cuda:0")
 REF = TorchRefBackend()
 
 
@@ -1044,3 +1045,91 @@ def test_igemm_groupnorm_statistics_epilogue(hip, case):
     with pytest.raises(ValueError):        # contract: the chunk count must match the path that writes the partials
         hip.igemm(dev(hip, x), dev(hip, w), o, taps=taps, pad=taps // 9, flags=L.EPI_GNSTAT, tile_m=tm, tile_n=tn,
                   gn_ws=hip.zeros((b * (nchunk + 1) * 64,), F32), gn_nchunk=nchunk + 1)
+
+
+# ------------------------------------------------------------------------------------------------ training / frame kernels
+@pytest.mark.parametrize("shape", [(3, 1, 7, 143), (2, 4, 8, 8), (5, 3, 187, 187)])
+def test_q_sample_is_bit_exact(hip, shape):
+    """dadd_q_sample_f32 against the torch ops: fp32 op for op in the reference's order with contraction off, so equality.
+    per_sample = 1001 is no multiple of the 256-thread block; 5 x 104907 = 524535 elements are more than the 2048 x 256
+    the grid holds at once (grid-stride loop); t hits 0 and 999."""
+    g = torch.Generator().manual_seed(31)
+    b = shape[0]
+    x0, noise = torch.randn(shape, generator=g), torch.randn(shape, generator=g)
+    t = torch.tensor([0, 999, 500, 17, 998])[:b]
+    ac = (1000 - torch.arange(1000)).float() * 65.0 / 65536.0       # 0.99 ... 0.001 in steps of 65 * 2^-16: exact on any host
+    # IEEE op for op on the host: the square roots through float64 (53 >= 2 * 24 + 2 bits: correctly rounded after the
+    # cast), because a host's vectorised fp32 sqrt need not be (measured on the GPU host: 177 to 344 of 1000 inputs one ulp
+    # off, while the kernel and torch on the device matched the correctly rounded root on all of them)
+    s0 = torch.sqrt(ac[t].double()).float().view(-1, 1, 1, 1)
+    s1 = torch.sqrt((1.0 - ac[t]).double()).float().view(-1, 1, 1, 1)
+    want = s0 * x0 + s1 * noise
+    out = hip.zeros(shape, F32)
+    xd, nd, td, acd = dev(hip, x0), dev(hip, noise), dev(hip, t), dev(hip, ac)
+    hip.q_sample(xd, nd, td, acd, out)
+    ref = hip.zeros(shape, F32)
+    with hip.ctx():                 # ... and the torch ops themselves, where the kernel runs
+        TorchRefBackend(DEV).q_sample(xd, nd, td, acd, ref)
+    hip.synchronize()
+    got = out.cpu()
+    print(f"q_sample {shape}: max |diff| to the host ops {(got - want).abs().max().item():.3e}, "
+          f"to the device ops {(got - ref.cpu()).abs().max().item():.3e}")
+    assert torch.equal(got, want)
+    assert torch.equal(got, ref.cpu())
+
+
+@pytest.mark.parametrize("per", [1, 255, 257, 4 * 64 * 64 + 3])
+def test_mse_rows(hip, per):
+    """dadd_mse_rows_f32 against float64 within per * 2^-24 * (sum d^2 / per): the fp32 sum of ``per`` terms in any order
+    (per - 1 additions) and the division, one rounding each.  That counts the summation only, so the first inputs sit on a
+    grid of 2^-8 in [-4, 4): d = pred - target and d^2 (at most 24 significant bits) are exact in fp32.  Gaussian inputs
+    add the roundings of d (twice in d^2) and of d^2: (per + 3) * 2^-24."""
+    g = torch.Generator().manual_seed(per)
+    b = 3
+    grid = lambda: torch.randint(-1024, 1024, (b, per), generator=g).float() / 256.0       # noqa: E731
+    for what, pred, target, nround in (("grid", grid(), grid(), per), ("gaussian", torch.randn(b, per, generator=g),
+                                                                      torch.randn(b, per, generator=g), per + 3)):
+        out = hip.zeros((b,), F32)
+        hip.mse_rows(dev(hip, pred), dev(hip, target), out)
+        hip.synchronize()
+        d2 = (pred.double() - target.double()) ** 2
+        want, bound = d2.mean(dim=1), nround * 2.0 ** -24 * d2.sum(dim=1) / per
+        err = (out.cpu().double() - want).abs()
+        print(f"mse_rows per {per} {what}: err / bound {(err / bound.clamp_min(1e-300)).max().item():.3f}")
+        assert bool((err <= bound).all()), (what, per, err.tolist(), bound.tolist())
+
+
+def _frames(shape, seed):
+    """Frames in [0, 1] whose x * 255 stays 2^-10 or more away from an integer (the fp32 product is off by at most
+    255 * 2^-24 = 1.5e-5, so truncation cannot fall on the other side), with exact 0.0 and 1.0 among them."""
+    g = torch.Generator().manual_seed(seed)
+    lvl = torch.randint(0, 255, shape, generator=g).double()
+    frac = 2.0 ** -9 + torch.rand(shape, generator=g, dtype=torch.float64) * (1.0 - 2.0 ** -8)
+    x = ((lvl + frac) / 255.0).float()
+    x.view(-1)[0::97] = 0.0
+    x.view(-1)[1::97] = 1.0
+    v = x.double() * 255.0
+    dist = (v - v.round()).abs()
+    edge = (x == 0.0) | (x == 1.0)
+    assert bool(((dist >= 2.0 ** -10) | edge).all()) and bool(edge.any())
+    return x
+
+
+@pytest.mark.parametrize("b,h,w", [(2, 6, 10), (3, 64, 64), (1, 2048, 2052)])
+def test_frames_to_u8(hip, b, h, w):
+    """dadd_frames_to_u8 equals ``permute(0, 2, 3, 1).mul(255).to(uint8)``: H*W = 60 is a multiple of 4 but not of the
+    block's 256 quads; 2048 x 2052 / 4 = 1050624 quads are more than the 4096 x 256 the grid holds at once."""
+    x = _frames((b, 3, h, w), 7 + b)
+    want = torch.zeros(b, h, w, 3, dtype=torch.uint8)
+    REF.frames_to_u8(x, want)
+    assert int(want.max()) == 255 and int(want.min()) == 0
+    out = hip.zeros((b, h, w, 3), torch.uint8)
+    hip.frames_to_u8(dev(hip, x), out)
+    hip.synchronize()
+    assert torch.equal(out.cpu(), want), int((out.cpu() != want).sum())
+
+
+def test_frames_to_u8_contract(hip):
+    x = dev(hip, torch.rand(1, 3, 3, 3))
+    with pytest.raises(ValueError, match="multiple of 4"):
+        hip.frames_to_u8(x, hip.zeros((1, 3, 3, 3), torch.uint8))

@@ -551,6 +551,34 @@ def test_unet_call_512_matches_oracle(hip, full_sd, bench_plan, monkeypatch):
     assert err < 1e-2 * max(1.0, ref.abs().max().item()), err
 
 
+def _u512_inputs():
+    g = torch.Generator().manual_seed(17)
+    return torch.randn(1, 4, 64, 64, generator=g), torch.randn(1, 48, 768, generator=g) * 0.5, torch.tensor([650])
+
+
+def test_unet_call_512_benchmark_batch_matches_oracle(hip, full_sd):
+    """The plan bench.py times, ``UNetPlan(4, 64)`` with its table-selected kernels and ``prepare_attn2``'s torch-side fold
+    of W_q / W_o into the conditioning, against the oracle: four copies of the B = 1 input above (samples are independent),
+    each row within the same 1e-2 * max(1, max|eps|) of the one cached oracle run.  The per-launch audit
+    (test_gpu_launch_audit.py) compares every launch but cannot see the fold; this closes that for the benchmark batch."""
+    from progressive_stable_diffusion_amd import engine as E
+    plan = E.UNetPlan(hip, full_sd, 4, 64)
+    names = [getattr(fn, "__name__", "") for fn, _, _ in plan.ops]
+    assert (names.count("ffn_block"), names.count("tf_head"), names.count("attn2_fused")) == (5, 5, 5)
+    x, cond, t = _u512_inputs()
+    if "u512" not in _ORACLE_RUNS:
+        torch.set_num_threads(min(os.cpu_count() or 1, 64))
+        with torch.no_grad():
+            _ORACLE_RUNS["u512"] = unet_forward(full_sd, x, t, cond, delta_scale=3.0)
+    ref = _ORACLE_RUNS["u512"]
+    got = plan.forward(x.expand(4, -1, -1, -1).contiguous().to(DEV), t.expand(4).contiguous().to(DEV),
+                       cond.expand(4, -1, -1).contiguous().to(DEV), lam=3.0)
+    hip.synchronize()
+    errs = [(got[i:i + 1].cpu() - ref).abs().max().item() for i in range(4)]
+    print(f"unet 512 call, benchmark batch: max err per row {['%.3e' % e for e in errs]} (max |eps| {ref.abs().max():.3f})")
+    assert max(errs) < 1e-2 * max(1.0, ref.abs().max().item()), errs
+
+
 def test_stochastic_sampler_on_device(full_sd):
     """eta > 0 (inference_pipeline_ip.py:457-468) through the HIP engine with injected per-step noise vs the oracle."""
     from progressive_stable_diffusion_amd import inference_pipeline_ip as PIPE

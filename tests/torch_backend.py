@@ -1,5 +1,5 @@
 """TEST-ONLY operator backend: the op contract of ``progressive_stable_diffusion_amd.backend``
-restated with plain torch on the CPU (fp16 storage, fp32 arithmetic).
+restated with plain torch (fp16 storage, fp32 arithmetic; on the CPU unless a device is given).
 
 Purpose: (1) let the CPU suite check the *wiring* of the engine's plans (which buffer feeds which
 op, weight packing, GEGLU interleave, skip order, split-K bookkeeping) against the oracle without
@@ -31,9 +31,20 @@ def geglu_deinterleave_index(n: int) -> torch.Tensor:
 class TorchRefBackend:
     name = "torch-ref"
 
-    def __init__(self, device="cpu"):
+    def __init__(self, device="cpu", compute=torch.float32):
+        """``compute``: the arithmetic type (fp32, as every test used it so far; float64 for the per-launch audit of
+        tests/launch_audit.py).  The rounding points that model a kernel's own 16-bit intermediates stay 16 bit in both."""
         self.device = torch.device(device)
+        self.compute = compute
         self.launches = 0
+
+    def c(self, t):
+        """``t`` in the arithmetic type."""
+        return t.to(self.compute)
+
+    def conv2d(self, x, w, bias=None, stride=1, padding=0):
+        """Every convolution of this backend (NCHW x OIHW, arithmetic type): one hook for the subclasses that restate it."""
+        return F.conv2d(x, w, bias, stride=stride, padding=padding)
 
     # plumbing -------------------------------------------------------------------------------
     def ctx(self):
@@ -67,27 +78,28 @@ class TorchRefBackend:
 
     # ops ------------------------------------------------------------------------------------
     def pack_latents(self, x, out, scale=1.0, mat=None, vec=None):
-        v = x.float() * scale
+        v = self.c(x) * scale
         if mat is not None:
-            v = torch.einsum("oc,bchw->bohw", mat.float(), v)
+            v = torch.einsum("oc,bchw->bohw", self.c(mat), v)
             if vec is not None:
-                v = v + vec.float()[None, :, None, None]
+                v = v + self.c(vec)[None, :, None, None]
         out.zero_()
         out[..., : x.shape[1]] = v.permute(0, 2, 3, 1).to(out.dtype)
 
     def conv_cin8(self, x, w, bias, out):
         co = w.shape[0]
-        wt = w.float().reshape(co, 3, 3, 8).permute(0, 3, 1, 2)
-        y = F.conv2d(x.float().permute(0, 3, 1, 2), wt, None if bias is None else bias.float(), padding=1)
+        wt = self.c(w).reshape(co, 3, 3, 8).permute(0, 3, 1, 2)
+        y = self.conv2d(self.c(x).permute(0, 3, 1, 2), wt, None if bias is None else self.c(bias), padding=1)
         out.copy_(y.permute(0, 2, 3, 1).to(out.dtype))
 
     def conv_in_nchw(self, x, w, bias, out, gn_ws=None, gn_nchunk=0):
-        x8 = torch.zeros(x.shape[0], x.shape[2], x.shape[3], 8, dtype=torch.float16)
+        # the fused kernel rounds the fp32 latents to the plan's storage type in registers (fp16, or bf16 in a bf16 plan)
+        x8 = torch.zeros(x.shape[0], x.shape[2], x.shape[3], 8, dtype=out.dtype, device=x.device)
         self.pack_latents(x, x8)
         self.conv_cin8(x8, w, bias, out)
         if gn_ws is not None:           # chunk partials of the rounded output, [B][nchunk][32][2]
             b, h, wd, c = out.shape
-            o = out.float().reshape(b, gn_nchunk, (h * wd) // gn_nchunk, 32, c // 32)
+            o = self.c(out).reshape(b, gn_nchunk, (h * wd) // gn_nchunk, 32, c // 32)
             st = torch.stack([o.sum(dim=(2, 4)), (o * o).sum(dim=(2, 4))], dim=-1)
             gn_ws[:b * gn_nchunk * 64].copy_(st.reshape(-1))
 
@@ -98,8 +110,8 @@ class TorchRefBackend:
 
     def conv_cout4(self, x, w, bias, out, mode=0):
         co, _, c = w.shape
-        wt = w.float().reshape(co, 3, 3, c).permute(0, 3, 1, 2)
-        y = F.conv2d(x.float().permute(0, 3, 1, 2), wt, None if bias is None else bias.float(), padding=1)
+        wt = self.c(w).reshape(co, 3, 3, c).permute(0, 3, 1, 2)
+        y = self.conv2d(self.c(x).permute(0, 3, 1, 2), wt, None if bias is None else self.c(bias), padding=1)
         if mode == 1:
             y = ((y.clamp(-1, 1) + 1.0) / 2.0).clamp(0, 1)
         elif mode == 2:
@@ -117,7 +129,7 @@ class TorchRefBackend:
         out.copy_(frames.permute(0, 2, 3, 1).mul(255).to(torch.uint8))
 
     def gaussian_sample(self, mean, logvar, noise, out, scale=1.0):
-        out.copy_((mean + torch.exp(0.5 * logvar.clamp(-30.0, 20.0)) * noise) * scale)
+        out.copy_((self.c(mean) + torch.exp(0.5 * self.c(logvar).clamp(-30.0, 20.0)) * self.c(noise)) * scale)
 
     def igemm(self, x, w, out, *, x2=None, bias=None, rowvec=None, residual=None, taps=1, stride=1,
               ups=0, pad=0, flags=0, splitk=1, partial=None, tile_n=0, tile_m=0, counters=None, ln_c1=None,
@@ -133,7 +145,7 @@ class TorchRefBackend:
                 s2 = ws2[: bsz * nch2 * 64].reshape(bsz, nch2, 32, 2).double().sum(dim=1)
                 r1, r2 = cgc // (c1_ // 32), cgc // (c2_ // 32)
                 cat = torch.cat([s1.reshape(bsz, 32 // r1, r1, 2).sum(dim=2), s2.reshape(bsz, 32 // r2, r2, 2).sum(dim=2)], dim=1)
-                wsc = cat.float().reshape(bsz, 1, 32, 2).contiguous().reshape(-1)
+                wsc = self.c(cat).reshape(bsz, 1, 32, 2).contiguous().reshape(-1)
                 xc = torch.cat([x, x2], dim=-1)
                 xn = torch.empty_like(xc)
                 self.groupnorm(xc, None, gam, bet, xn, wsc, 32, eps_in, 1 if flags & 16384 else 0, ws_chunks=1)
@@ -142,7 +154,7 @@ class TorchRefBackend:
                 xn = torch.empty_like(x)
                 self.groupnorm(x, None, gam, bet, xn, ws_in, 32, eps_in, 1 if flags & 16384 else 0, ws_chunks=nch_in)
                 x = xn
-        xin = x.float() if x2 is None else torch.cat([x.float(), x2.float()], dim=-1)
+        xin = self.c(x) if x2 is None else torch.cat([self.c(x), self.c(x2)], dim=-1)
         b, hi, wi, cin = xin.shape
         n = w.shape[0]
         assert cin % 64 == 0 and x.shape[-1] % 64 == 0 and n % 8 == 0
@@ -152,29 +164,29 @@ class TorchRefBackend:
         if ups:
             xn = F.interpolate(xn, scale_factor=2.0, mode="nearest")
         k = 3 if taps == 9 else 1
-        wt = w.float().reshape(n, k, k, cin).permute(0, 3, 1, 2)
+        wt = self.c(w).reshape(n, k, k, cin).permute(0, 3, 1, 2)
         if pad == 0 and k == 3:       # asymmetric (0,1,0,1) padding of the VAE-encoder downsample
             xn = F.pad(xn, (0, 2, 0, 2))
-            y = F.conv2d(xn, wt, None, stride=stride)[:, :, :ho, :wo]
+            y = self.conv2d(xn, wt, None, stride=stride)[:, :, :ho, :wo]
         else:
-            y = F.conv2d(xn, wt, None, stride=stride, padding=pad)
+            y = self.conv2d(xn, wt, None, stride=stride, padding=pad)
         assert y.shape[2] == ho and y.shape[3] == wo, (y.shape, out.shape)
         y = y.permute(0, 2, 3, 1)
         if flags & 128:                 # EPI_LNFOLD: rstd * (x (gamma o W)^T - mu * c1), statistics of the fp16 rows
             if ln_stats_in is not None:     # row partials [P][M][2] written by the producer of x (EPI_LNSTAT)
-                st = ln_stats_in.sum(dim=0).reshape(b, hi, wi, 2) / cin
+                st = self.c(ln_stats_in).sum(dim=0).reshape(b, hi, wi, 2) / cin
                 mu, var = st[..., 0:1], st[..., 1:2] - st[..., 0:1] ** 2
             else:
                 mu = xin.mean(dim=-1, keepdim=True)
                 var = (xin * xin).mean(dim=-1, keepdim=True) - mu * mu
-            y = torch.rsqrt(var.clamp_min(0.0) + ln_eps) * (y - mu * ln_c1.float())
+            y = torch.rsqrt(var.clamp_min(0.0) + ln_eps) * (y - mu * self.c(ln_c1))
         act = flags & (256 | 512 | 1024)
         gn_apply_silu = bool(flags & EPI_GNAPPLY_SILU)
         flags &= 15                     # tuning bits (16, 32) do not change the math
         if flags & EPI_BIAS:
-            y = y + bias.float()
+            y = y + self.c(bias)
         if flags & EPI_ROWVEC:
-            y = y + rowvec.float()[:, None, None, :]
+            y = y + self.c(rowvec)[:, None, None, :]
         if act & 256:
             y = y * torch.sigmoid(1.702 * y)
         elif act & 512:
@@ -182,17 +194,17 @@ class TorchRefBackend:
         elif act & 1024:
             y = torch.sigmoid(y)
         if flags & EPI_GEGLU:
-            y = y[..., geglu_deinterleave_index(n).argsort()]   # undo the physical row order
+            y = y[..., geglu_deinterleave_index(n).argsort().to(y.device)]   # undo the physical row order
             hid, gate = y.chunk(2, dim=-1)
             y = hid * F.gelu(gate)
         if flags & EPI_RESIDUAL:
-            y = y + residual.float()
+            y = y + self.c(residual)
         out.copy_(y.to(out.dtype))
         if ln_stats_out is not None:    # EPI_LNSTAT: row partials of the rounded output over blocks of N / P columns
-            o = out.float().reshape(b * ho * wo, ln_stats_out.shape[0], -1)
+            o = self.c(out).reshape(b * ho * wo, ln_stats_out.shape[0], -1)
             ln_stats_out.copy_(torch.stack([o.sum(dim=-1), (o * o).sum(dim=-1)], dim=-1).permute(1, 0, 2))
         if gn_ws is not None:           # EPI_GNSTAT: chunk partials of the rounded output, [B][nchunk][32][2]
-            o = out.float().reshape(b, gn_nchunk, -1, 32, n // 32)
+            o = self.c(out).reshape(b, gn_nchunk, -1, 32, n // 32)
             part = torch.stack([o.sum(dim=(2, 4)), (o * o).sum(dim=(2, 4))], dim=-1)
             gn_ws[: part.numel()].copy_(part.reshape(-1))
         if gn_apply is not None:        # EPI_GNAPPLY: GroupNorm (+ SiLU) of the rounded output, written beside it
@@ -206,7 +218,7 @@ class TorchRefBackend:
         pass
 
     def groupnorm(self, x1, x2, gamma, beta, out, ws, groups, eps, silu, ws_chunks=0):
-        x = x1.float() if x2 is None else torch.cat([x1.float(), x2.float()], dim=-1)
+        x = self.c(x1) if x2 is None else torch.cat([self.c(x1), self.c(x2)], dim=-1)
         if ws_chunks:                   # statistics come from the producer's partials, not from x
             b, c = x.shape[0], x.shape[-1]
             part = ws[: b * ws_chunks * groups * 2].reshape(b, ws_chunks, groups, 2).double().sum(dim=1)
@@ -214,41 +226,41 @@ class TorchRefBackend:
             mean = part[..., 0] / cnt
             rstd = torch.rsqrt((part[..., 1] / cnt - mean * mean).clamp_min(0) + eps)
             xg = x.reshape(b, -1, groups, c // groups)
-            y = ((xg - mean.float()[:, None, :, None]) * rstd.float()[:, None, :, None]).reshape(x.shape)
-            y = (y * gamma.float() + beta.float()).permute(0, 3, 1, 2)
+            y = ((xg - self.c(mean)[:, None, :, None]) * self.c(rstd)[:, None, :, None]).reshape(x.shape)
+            y = (y * self.c(gamma) + self.c(beta)).permute(0, 3, 1, 2)
         else:
-            y = F.group_norm(x.permute(0, 3, 1, 2), groups, gamma.float(), beta.float(), eps)
+            y = F.group_norm(x.permute(0, 3, 1, 2), groups, self.c(gamma), self.c(beta), eps)
         if silu:
             y = F.silu(y)
         out.copy_(y.permute(0, 2, 3, 1).to(out.dtype))
 
     def layernorm(self, x, gamma, beta, out, eps=1e-5):
-        out.copy_(F.layer_norm(x.float(), (x.shape[-1],), gamma.float(), beta.float(), eps).to(out.dtype))
+        out.copy_(F.layer_norm(self.c(x), (x.shape[-1],), self.c(gamma), self.c(beta), eps).to(out.dtype))
 
     def self_attn(self, qkv, out, heads):
         b, n, c3 = qkv.shape
         c = c3 // 3
         d = c // heads
-        q, k, v = (t.float().view(b, n, heads, d).transpose(1, 2) for t in qkv.split(c, dim=-1))
+        q, k, v = (self.c(t).view(b, n, heads, d).transpose(1, 2) for t in qkv.split(c, dim=-1))
         p = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(d), dim=-1)
         out.copy_((p @ v).transpose(1, 2).reshape(b, n, c).to(out.dtype))
 
     def attn2_fused(self, x, mcat, vw, bias, residual, out, ln_stats_out=None, ln_stats_in=None, ln_c1=None, ln_d=None,
                     ln_eps=1e-5):
         b, hw, c = x.shape
-        s = torch.einsum("bmc,bkc->bmk", x.float(), mcat.float())            # log2(e)/sqrt(d) folded in
+        s = torch.einsum("bmc,bkc->bmk", self.c(x), self.c(mcat))            # log2(e)/sqrt(d) folded in
         if ln_stats_in is not None:     # norm2 folded in: S = rstd (x mcat^T - mu c1) + d
-            st = ln_stats_in.sum(dim=0).reshape(b, hw, 2) / c
+            st = self.c(ln_stats_in).sum(dim=0).reshape(b, hw, 2) / c
             mu, var = st[..., 0:1], (st[..., 1:2] - st[..., 0:1] ** 2).clamp_min(0.0)
-            s = torch.rsqrt(var + ln_eps) * (s - mu * ln_c1.float()[:, None, :]) + ln_d.float()[:, None, :]
+            s = torch.rsqrt(var + ln_eps) * (s - mu * self.c(ln_c1)[:, None, :]) + self.c(ln_d)[:, None, :]
         pr = torch.softmax(s.view(b, hw, 24, 16) * math.log(2.0), dim=-1).view(b, hw, 384)
-        pr = pr.to(torch.float16).float()                                     # P is stored in fp16
-        y = torch.einsum("bmk,bnk->bmn", pr, vw.float())
+        pr = self.c(pr.to(torch.float16))                                     # P is stored in fp16
+        y = torch.einsum("bmk,bnk->bmn", pr, self.c(vw))
         if bias is not None:
-            y = y + bias.float()
-        out.copy_((y + residual.float()).to(out.dtype))
+            y = y + self.c(bias)
+        out.copy_((y + self.c(residual)).to(out.dtype))
         if ln_stats_out is not None:
-            o = out.float().reshape(b * hw, ln_stats_out.shape[0], -1)
+            o = self.c(out).reshape(b * hw, ln_stats_out.shape[0], -1)
             ln_stats_out.copy_(torch.stack([o.sum(dim=-1), (o * o).sum(dim=-1)], dim=-1).permute(1, 0, 2))
 
     @staticmethod
@@ -289,19 +301,23 @@ class TorchRefBackend:
         assert off == st.numel()
         return w1, bias, w2, wp
 
+    def _unpacked(self, fn, stream, *rest):
+        """The weights of a piece stream where (and in the type in which) this backend computes."""
+        return tuple(t.to(device=stream.device, dtype=self.compute) for t in fn(stream, *rest))
+
     def ffn_block(self, x, stream, ln_g, ln_b, b1, b2, bp, xres, out, gn_ws=None, gn_nchunk=0, ln_eps=1e-5):
         """csrc/ffn_block.hip in torch: the four rounding points of the unfused launches (normalised rows, GEGLU output,
-        h4, result), everything else fp32."""
+        h4, result), everything else in the arithmetic type."""
         import torch.nn.functional as Fn
         b, hw, c = x.shape
-        w1, b1u, w2, wp = self.unpack_ffn_stream(stream, b1)
-        xn = Fn.layer_norm(x.float(), (c,), ln_g.float(), ln_b.float(), ln_eps).to(torch.float16).float()
+        w1, b1u, w2, wp = self._unpacked(self.unpack_ffn_stream, stream, b1)
+        xn = self.c(Fn.layer_norm(self.c(x), (c,), self.c(ln_g), self.c(ln_b), ln_eps).to(torch.float16))
         h = xn @ w1.T + b1u
-        gg = (h[..., :1280] * Fn.gelu(h[..., 1280:])).to(torch.float16).float()
-        h4 = (gg @ w2.T + b2.float() + x.float()).to(torch.float16).float()
-        out.copy_((h4 @ wp.T + bp.float() + xres.float()).to(out.dtype))
+        gg = self.c((h[..., :1280] * Fn.gelu(h[..., 1280:])).to(torch.float16))
+        h4 = self.c((gg @ w2.T + self.c(b2) + self.c(x)).to(torch.float16))
+        out.copy_((h4 @ wp.T + self.c(bp) + self.c(xres)).to(out.dtype))
         if gn_ws is not None:
-            o = out.float().reshape(b, gn_nchunk, hw // gn_nchunk, 32, c // 32)
+            o = self.c(out).reshape(b, gn_nchunk, hw // gn_nchunk, 32, c // 32)
             st = torch.stack([o.sum(dim=(2, 4)), (o * o).sum(dim=(2, 4))], dim=-1)      # [b][chunk][32][2]
             gn_ws[:b * gn_nchunk * 64].copy_(st.reshape(-1))
 
@@ -328,17 +344,18 @@ class TorchRefBackend:
         (fp16 hs), LayerNorm 1 (fp16), q|k|v (fp16)."""
         import torch.nn.functional as Fn
         b, hw, c = x.shape
-        wp, wqkv = self.unpack_head_stream(stream)
+        wp, wqkv = self._unpacked(self.unpack_head_stream, stream)
         st = gn_ws[:b * gn_nchunk * 64].double().reshape(b, gn_nchunk, 32, 2).sum(dim=1)
         n = hw * (c // 32)
         mu = st[..., 0] / n
         rstd = 1.0 / torch.sqrt((st[..., 1] / n - mu * mu).clamp_min(0.0) + gn_eps)
-        sc = rstd.float().repeat_interleave(c // 32, dim=1) * gn_g.float()                 # [b][c]
-        sh = gn_b.float() - mu.float().repeat_interleave(c // 32, dim=1) * sc
-        g = (x.float() * sc[:, None, :] + sh[:, None, :]).to(torch.float16).float()
-        h = (g @ wp.T + bp.float()).to(torch.float16)
-        hs.copy_(h)
-        ln = Fn.layer_norm(h.float(), (c,), ln_g.float(), ln_b.float(), ln_eps).to(torch.float16).float()
+        sc = self.c(rstd).repeat_interleave(c // 32, dim=1) * self.c(gn_g)                 # [b][c]
+        sh = self.c(gn_b) - self.c(mu).repeat_interleave(c // 32, dim=1) * sc
+        g = self.c((self.c(x) * sc[:, None, :] + sh[:, None, :]).to(torch.float16))
+        hraw = g @ wp.T + self.c(bp)
+        hs.copy_(hraw.to(hs.dtype))
+        h = hraw.to(torch.float16)                                                         # the rows LayerNorm 1 reads
+        ln = self.c(Fn.layer_norm(self.c(h), (c,), self.c(ln_g), self.c(ln_b), ln_eps).to(torch.float16))
         qkv.copy_((ln @ wqkv.T).to(qkv.dtype))
 
     def tri_xattn(self, q, kv, out, gates, lam, mode, heads, lam_dev=None):
@@ -346,15 +363,15 @@ class TorchRefBackend:
             lam = float(lam_dev.reshape(-1)[0])
         b, n, c = q.shape
         d = c // heads
-        qh = q.float().view(b, n, heads, d).transpose(1, 2)
+        qh = self.c(q).view(b, n, heads, d).transpose(1, 2)
 
         def path(tok0, ntok, kcol, vcol):
-            k = kv[:, tok0:tok0 + ntok, kcol:kcol + c].float().view(b, ntok, heads, d).transpose(1, 2)
-            v = kv[:, tok0:tok0 + ntok, vcol:vcol + c].float().view(b, ntok, heads, d).transpose(1, 2)
+            k = self.c(kv[:, tok0:tok0 + ntok, kcol:kcol + c]).view(b, ntok, heads, d).transpose(1, 2)
+            v = self.c(kv[:, tok0:tok0 + ntok, vcol:vcol + c]).view(b, ntok, heads, d).transpose(1, 2)
             return torch.softmax(qh @ k.transpose(-1, -2) / math.sqrt(d), dim=-1) @ v
 
         if mode == 0:
-            z = gates[0].float() * path(16, 16, 0, c) + gates[1].float() * path(0, 16, 2 * c, 3 * c)
+            z = self.c(gates[0]) * path(16, 16, 0, c) + self.c(gates[1]) * path(0, 16, 2 * c, 3 * c)
             if lam != 0.0:
                 z = z + lam * path(32, 16, 2 * c, 3 * c)
         else:
@@ -363,19 +380,19 @@ class TorchRefBackend:
 
     def timestep_features(self, t, out):
         half = out.shape[1] // 2
-        freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)
-        ang = t.float()[:, None] * freqs[None, :]
+        freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=self.compute, device=t.device) / half)
+        ang = self.c(t)[:, None] * freqs[None, :]
         out.copy_(torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1))
 
     def linear_rows(self, x, w, bias, out, act_in=0, act_out=0):
         act = {0: lambda t: t, 1: F.silu, 2: F.gelu}
-        y = F.linear(act[act_in](x.float()), w.float(), None if bias is None else bias.float())
+        y = F.linear(act[act_in](self.c(x)), self.c(w), None if bias is None else self.c(bias))
         out.copy_(act[act_out](y))
 
     def attention(self, q, k, v, out, heads):
         b, nq, c = out.shape
         d = c // heads
-        qh, kh, vh = (t[..., :c].float().reshape(b, t.shape[1], heads, d).transpose(1, 2) for t in (q, k, v))
+        qh, kh, vh = (self.c(t[..., :c]).reshape(b, t.shape[1], heads, d).transpose(1, 2) for t in (q, k, v))
         p = torch.softmax(qh @ kh.transpose(-1, -2) / math.sqrt(d), dim=-1)
         out.copy_((p @ vh).transpose(1, 2).reshape(b, nq, c).to(out.dtype))
 
