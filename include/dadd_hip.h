@@ -132,6 +132,23 @@ typedef struct {
 } dadd_igemm_desc;
 int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream);
 
+/* What dadd_conv_igemm_f16 would launch for `d` on a device with `num_cu` compute units: the same validation and the
+ * same decisions, no launch, no HIP call, no access to the buffers `d` points to (host-only; works without a GPU).
+ * Returns what the launch would return; on DADD_OK fills `out`.  The names are the profiler's kernel names (static
+ * strings owned by the library). */
+typedef struct {
+  const char* kernel;            /* the GEMM / conv kernel */
+  const char* finish;            /* the split-K finish kernel launched behind it, NULL when there is none */
+  int32_t tile_m, tile_n;        /* the output tile actually used */
+  int32_t nsplit, kps;           /* K slices (grid_y of a non-persistent launch) and K tiles (halo kernel: 64-channel chunks) per slice */
+  int32_t persistent;            /* 1: the LDS-DMA ring runs over several output tiles per workgroup (grid_x = num_cu) */
+  int32_t grid_x, grid_y, block; /* launch geometry of `kernel` */
+  int32_t smem;                  /* its dynamic LDS bytes */
+  int32_t gm, gn;                /* tile order: groups of gm x gn tiles (0: column tile fastest) */
+} dadd_igemm_choice;
+int dadd_conv_igemm_resolve_f16(const dadd_igemm_desc* d, int num_cu, dadd_igemm_choice* out);
+/* the bf16 sibling (same arguments, the *_bf16 kernel names) is declared in dadd_hip_host.h */
+
 /* ---- the two thin-channel convolutions at the UNet / VAE ends ------------------------------
  * conv_in : x fp16 NHWC with 8 stored channels (4 or 3 real) -> fp16 NHWC Cout.
  * conv_out: fp16 NHWC C -> fp32 NCHW Cout<=4; mode 1 also applies clamp(-1,1),(x+1)/2,clamp(0,1)

@@ -38,6 +38,64 @@ def _sfx(*ts) -> str:
     return _SFX[kinds.pop()]
 
 
+def fill_igemm_desc(d, ptr, x, w, out, *, x2=None, bias=None, rowvec=None, residual=None, taps=1, stride=1,
+                    ups=0, pad=0, flags=0, splitk=1, partial=None, tile_n=0, tile_m=0, counters=None, ln_c1=None,
+                    ln_eps=1e-5, gn_ws=None, gn_nchunk=0, ln_stats_out=None, ln_stats_in=None, gn_in=None, gn_apply=None):
+    """Check the shapes of one ``igemm`` call (arguments of ``HipBackend.igemm``) and fill the ``IgemmDesc`` ``d`` with
+    it; ``ptr`` turns a tensor (or None) into the address the descriptor carries."""
+    b, hi, wi, c1 = x.shape
+    c2 = 0 if x2 is None else x2.shape[-1]
+    n = w.shape[0]
+    ho, wo = out.shape[1], out.shape[2]
+    assert w.shape[1] == taps * (c1 + c2), (w.shape, taps, c1, c2)
+    assert out.shape[-1] == (n // 2 if flags & L.EPI_GEGLU else n) and out.shape[0] == b
+    d.x, d.x2, d.w, d.out, d.partial = ptr(x), ptr(x2), ptr(w), ptr(out), ptr(partial)
+    d.bias, d.rowvec, d.residual = ptr(bias), ptr(rowvec), ptr(residual)
+    d.B, d.Hi, d.Wi, d.C1, d.C2, d.Ho, d.Wo, d.N = b, hi, wi, c1, c2, ho, wo, n
+    d.taps, d.stride, d.ups, d.pad = taps, stride, ups, pad
+    d.ldo, d.ldr = out.stride(-2), (residual.stride(-2) if residual is not None else 0)
+    d.ld_rowvec = rowvec.stride(0) if rowvec is not None else 0
+    d.splitk, d.flags, d.tile_n, d.tile_m = splitk, flags, tile_n, tile_m
+    d.counters = ptr(counters)
+    d.ln_c1, d.ln_eps = ptr(ln_c1), float(ln_eps)
+    d.gn_ws, d.gn_nchunk, d.gn_cg = ptr(gn_ws), int(gn_nchunk), (n // 32 if gn_ws is not None else 0)
+    if gn_ws is not None:
+        assert flags & L.EPI_GNSTAT and gn_ws.numel() >= b * gn_nchunk * 64 and gn_ws.dtype == torch.float32
+    if ln_c1 is not None:
+        assert flags & L.EPI_LNFOLD and ln_c1.numel() == n and ln_c1.dtype == torch.float32
+    m_rows = b * ho * wo
+    d.ln_stats_out, d.ln_stats_in, d.ln_parts_out, d.ln_parts_in = ptr(ln_stats_out), ptr(ln_stats_in), 0, 0
+    if ln_stats_out is not None:
+        assert flags & L.EPI_LNSTAT and ln_stats_out.dtype == torch.float32 and ln_stats_out.dim() == 3 \
+            and ln_stats_out.shape[1:] == (m_rows, 2) and ln_stats_out.is_contiguous()
+        d.ln_parts_out = ln_stats_out.shape[0]
+    if ln_stats_in is not None:
+        assert flags & L.EPI_LNFOLD and ln_stats_in.dtype == torch.float32 and ln_stats_in.dim() == 3 \
+            and ln_stats_in.shape[1:] == (b * hi * wi, 2) and ln_stats_in.is_contiguous()
+        d.ln_parts_in = ln_stats_in.shape[0]
+    d.gn_in_ws = d.gn_in_gamma = d.gn_in_beta = d.gn_in_ws2 = None
+    d.gn_in_nchunk, d.gn_in_eps, d.gn_in_nchunk2 = 0, 0.0, 0
+    if gn_in is not None:       # (partials, chunks, gamma, beta, eps[, partials of x2, chunks of x2])
+        ws_in, nch_in, gam, bet, eps_in = gn_in[:5]
+        assert flags & L.PRE_GN and ws_in.dtype == gam.dtype == bet.dtype == torch.float32 \
+            and ws_in.numel() >= b * nch_in * 64 and gam.numel() == c1 + c2 and bet.numel() == c1 + c2
+        d.gn_in_ws, d.gn_in_gamma, d.gn_in_beta = ptr(ws_in), ptr(gam), ptr(bet)
+        d.gn_in_nchunk, d.gn_in_eps = int(nch_in), float(eps_in)
+        if len(gn_in) > 5:
+            ws2, nch2 = gn_in[5], gn_in[6]
+            assert x2 is not None and ws2.dtype == torch.float32 and ws2.numel() >= b * nch2 * 64
+            d.gn_in_ws2, d.gn_in_nchunk2 = ptr(ws2), int(nch2)
+    d.gn_out = d.gn_out_gamma = d.gn_out_beta = None
+    d.gn_out_eps = 0.0
+    if gn_apply is not None:
+        g_out, gam, bet, eps_o = gn_apply
+        assert flags & L.EPI_GNAPPLY and g_out.shape == out.shape and g_out.dtype == out.dtype and g_out.is_contiguous() \
+            and gam.dtype == bet.dtype == torch.float32 and gam.numel() == n and bet.numel() == n
+        d.gn_out, d.gn_out_gamma, d.gn_out_beta, d.gn_out_eps = ptr(g_out), ptr(gam), ptr(bet), float(eps_o)
+    if partial is not None:
+        assert partial.numel() >= splitk * b * ho * wo * n
+
+
 class HipBackend:
     name = "hip-gfx950"
 
@@ -181,59 +239,12 @@ class HipBackend:
         ``gn_in`` = (partials [B*nchunk*64] fp32, nchunk, gamma, beta, eps) with PRE_GN: GroupNorm of x on the way in.
         ``ln_stats_out`` [P][M][2] fp32 (EPI_LNSTAT): row partials of the output, P = N / (tile_n/2);
         ``ln_stats_in`` [P'][M][2] (EPI_LNFOLD): the partials of x written by its producer."""
-        b, hi, wi, c1 = x.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
-        n = w.shape[0]
         fn = getattr(self.lib, "dadd_conv_igemm_" + _sfx(x, x2, w, out, residual, None if gn_apply is None else gn_apply[0]))
-        ho, wo = out.shape[1], out.shape[2]
-        assert w.shape[1] == taps * (c1 + c2), (w.shape, taps, c1, c2)
-        assert out.shape[-1] == (n // 2 if flags & L.EPI_GEGLU else n) and out.shape[0] == b
         d = self._desc
-        d.x, d.x2, d.w, d.out, d.partial = _p(x), _p(x2), _p(w), _p(out), _p(partial)
-        d.bias, d.rowvec, d.residual = _p(bias), _p(rowvec), _p(residual)
-        d.B, d.Hi, d.Wi, d.C1, d.C2, d.Ho, d.Wo, d.N = b, hi, wi, c1, c2, ho, wo, n
-        d.taps, d.stride, d.ups, d.pad = taps, stride, ups, pad
-        d.ldo, d.ldr = out.stride(-2), (residual.stride(-2) if residual is not None else 0)
-        d.ld_rowvec = rowvec.stride(0) if rowvec is not None else 0
-        d.splitk, d.flags, d.tile_n, d.tile_m = splitk, flags, tile_n, tile_m
-        d.counters = _p(counters)
-        d.ln_c1, d.ln_eps = _p(ln_c1), float(ln_eps)
-        d.gn_ws, d.gn_nchunk, d.gn_cg = _p(gn_ws), int(gn_nchunk), (n // 32 if gn_ws is not None else 0)
-        if gn_ws is not None:
-            assert flags & L.EPI_GNSTAT and gn_ws.numel() >= b * gn_nchunk * 64 and gn_ws.dtype == torch.float32
-        if ln_c1 is not None:
-            assert flags & L.EPI_LNFOLD and ln_c1.numel() == n and ln_c1.dtype == torch.float32
-        m_rows = b * ho * wo
-        d.ln_stats_out, d.ln_stats_in, d.ln_parts_out, d.ln_parts_in = _p(ln_stats_out), _p(ln_stats_in), 0, 0
-        if ln_stats_out is not None:
-            assert flags & L.EPI_LNSTAT and ln_stats_out.dtype == torch.float32 and ln_stats_out.dim() == 3 \
-                and ln_stats_out.shape[1:] == (m_rows, 2) and ln_stats_out.is_contiguous()
-            d.ln_parts_out = ln_stats_out.shape[0]
-        if ln_stats_in is not None:
-            assert flags & L.EPI_LNFOLD and ln_stats_in.dtype == torch.float32 and ln_stats_in.dim() == 3 \
-                and ln_stats_in.shape[1:] == (b * hi * wi, 2) and ln_stats_in.is_contiguous()
-            d.ln_parts_in = ln_stats_in.shape[0]
-        d.gn_in_ws = d.gn_in_gamma = d.gn_in_beta = d.gn_in_ws2 = None
-        d.gn_in_nchunk, d.gn_in_eps, d.gn_in_nchunk2 = 0, 0.0, 0
-        if gn_in is not None:       # (partials, chunks, gamma, beta, eps[, partials of x2, chunks of x2])
-            ws_in, nch_in, gam, bet, eps_in = gn_in[:5]
-            assert flags & L.PRE_GN and ws_in.dtype == gam.dtype == bet.dtype == torch.float32 \
-                and ws_in.numel() >= b * nch_in * 64 and gam.numel() == c1 + c2 and bet.numel() == c1 + c2
-            d.gn_in_ws, d.gn_in_gamma, d.gn_in_beta = _p(ws_in), _p(gam), _p(bet)
-            d.gn_in_nchunk, d.gn_in_eps = int(nch_in), float(eps_in)
-            if len(gn_in) > 5:
-                ws2, nch2 = gn_in[5], gn_in[6]
-                assert x2 is not None and ws2.dtype == torch.float32 and ws2.numel() >= b * nch2 * 64
-                d.gn_in_ws2, d.gn_in_nchunk2 = _p(ws2), int(nch2)
-        d.gn_out = d.gn_out_gamma = d.gn_out_beta = None
-        d.gn_out_eps = 0.0
-        if gn_apply is not None:
-            g_out, gam, bet, eps_o = gn_apply
-            assert flags & L.EPI_GNAPPLY and g_out.shape == out.shape and g_out.dtype == out.dtype and g_out.is_contiguous() \
-                and gam.dtype == bet.dtype == torch.float32 and gam.numel() == n and bet.numel() == n
-            d.gn_out, d.gn_out_gamma, d.gn_out_beta, d.gn_out_eps = _p(g_out), _p(gam), _p(bet), float(eps_o)
-        if partial is not None:
-            assert partial.numel() >= splitk * b * ho * wo * n
+        fill_igemm_desc(d, _p, x, w, out, x2=x2, bias=bias, rowvec=rowvec, residual=residual, taps=taps, stride=stride,
+                        ups=ups, pad=pad, flags=flags, splitk=splitk, partial=partial, tile_n=tile_n, tile_m=tile_m,
+                        counters=counters, ln_c1=ln_c1, ln_eps=ln_eps, gn_ws=gn_ws, gn_nchunk=gn_nchunk,
+                        ln_stats_out=ln_stats_out, ln_stats_in=ln_stats_in, gn_in=gn_in, gn_apply=gn_apply)
         L.check(fn(C.byref(d), self.s))
 
     # -- training backward of the matrix products (csrc/wgrad.hip; the data gradient is the forward kernel)

@@ -5,6 +5,7 @@
 #define DADD_BF16 1
 
 #define IgemmArgs IgemmArgs_bf16
+#define IgemmLaunch IgemmLaunch_bf16
 
 // kernels (rocprofv3 and the launch tags show the _bf16 names)
 #define igemm_kernel igemm_kernel_bf16
@@ -29,17 +30,18 @@
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
 #define dadd_init_igemm_dma dadd_init_igemm_dma_bf16
-#define dadd_launch_igemm_dma dadd_launch_igemm_dma_bf16
-#define dadd_igemm_dma_persistent dadd_igemm_dma_persistent_bf16
+#define dadd_igemm_dma_row dadd_igemm_dma_row_bf16
+#define dadd_igemm_resolve dadd_igemm_resolve_bf16
 #define dadd_init_conv_halo dadd_init_conv_halo_bf16
 #define dadd_conv_halo_applicable dadd_conv_halo_applicable_bf16
 #define dadd_conv_halo_gn_channels dadd_conv_halo_gn_channels_bf16
-#define dadd_launch_conv_halo dadd_launch_conv_halo_bf16
+#define dadd_conv_halo_row dadd_conv_halo_row_bf16
 #define dadd_init_norm dadd_init_norm_bf16
 #define dadd_init_attention dadd_init_attention_bf16
 
 // C entry points (include/dadd_hip.h)
 #define dadd_conv_igemm_f16 dadd_conv_igemm_bf16
+#define dadd_conv_igemm_resolve_f16 dadd_conv_igemm_resolve_bf16
 #define dadd_groupnorm_f16 dadd_groupnorm_bf16
 #define dadd_layernorm_f16 dadd_layernorm_bf16
 #define dadd_attn_f16 dadd_attn_bf16

@@ -508,27 +508,23 @@ __global__ __launch_bounds__(DUO ? 768 : 512, 1) void conv3x3_halo_kernel(const 
 #endif
 }
 
-template <int WT, bool DUO, bool GNIN = false>
-int set_attr_halo() {
-  DADD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<WT, DUO, GNIN>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, GNIN ? SMEM_BYTES_GNIN : SMEM_BYTES));
-  return DADD_OK;
-}
+// kernel table (igemm_args.h): WT, DUO, GNIN
+#define HALO_ROW(WT, DUO, GNIN)                                                                          \
+  {DADD_KNAME("conv3x3_halo_kernel") "<" #WT ", " #DUO ", " #GNIN ">", conv3x3_halo_kernel<WT, DUO, GNIN>, \
+   DUO ? 768 : 512, GNIN ? SMEM_BYTES_GNIN : SMEM_BYTES, {WT, DUO, GNIN}}
+const IgemmKernel HALO_KERNELS[] = {
+    HALO_ROW(64, false, true),  HALO_ROW(32, false, true),  HALO_ROW(16, false, true),
+    HALO_ROW(64, true, false),  HALO_ROW(32, true, false),  HALO_ROW(16, true, false),
+    HALO_ROW(64, false, false), HALO_ROW(32, false, false), HALO_ROW(16, false, false),
+};
+#undef HALO_ROW
 
 }  // namespace
 
-int dadd_init_conv_halo() {
-  int rc = set_attr_halo<64, false>();
-  if (rc == DADD_OK) rc = set_attr_halo<32, false>();
-  if (rc == DADD_OK) rc = set_attr_halo<16, false>();
-  if (rc == DADD_OK) rc = set_attr_halo<64, true>();
-  if (rc == DADD_OK) rc = set_attr_halo<32, true>();
-  if (rc == DADD_OK) rc = set_attr_halo<16, true>();
-  if (rc == DADD_OK) rc = set_attr_halo<64, false, true>();
-  if (rc == DADD_OK) rc = set_attr_halo<32, false, true>();
-  if (rc == DADD_OK) rc = set_attr_halo<16, false, true>();
-  return rc;
-}
+int dadd_init_conv_halo() { return dadd_set_max_lds(HALO_KERNELS); }
+
+// DUO is the A/B build (DADD_TUNE_SHALLOW): measured equal to the one-wave build (see the kernel comment)
+const IgemmKernel* dadd_conv_halo_row(int Wo, bool duo, bool gn_in) { return dadd_find_row(HALO_KERNELS, Wo, duo, gn_in); }
 
 // DADD_PRE_GN: input channels whose (scale, shift) fit in LDS for a map of width Wo
 int dadd_conv_halo_gn_channels(int Wo) {
@@ -541,29 +537,4 @@ bool dadd_conv_halo_applicable(const IgemmArgs& a, int tile_n) {
          a.Hi == a.Ho && a.Wi == a.Wo && (a.Wo == 16 || a.Wo == 32 || a.Wo == 64) &&
          (a.Ho * a.Wo) % BM == 0 && (BM / a.Wo + 2) * (a.Wo + 2) <= HALO_MAX_PIX &&
          !(a.flags & (DADD_EPI_GEGLU | DADD_TUNE_PERSIST));
-}
-
-// `a.kps` = chunks per K slice, `a.splitk` = nsplit (set by the caller).
-int dadd_launch_conv_halo(const IgemmArgs& a, int nsplit, hipStream_t s) {
-  DADD_REQUIRE((size_t)a.B * a.Hi * a.Wi * (size_t)(a.C1 > a.C2 ? a.C1 : a.C2) * 2 < 0x7FF00000ull &&
-                   (size_t)a.N * a.K * 2 < 0x7FF00000ull,
-               "conv_halo: operand larger than the 2 GiB buffer window");
-  dim3 grid(a.mtiles * a.ntiles, nsplit);
-  const double flop = dadd_igemm_flop(a), bytes = dadd_igemm_bytes(a);
-  const bool duo = (a.flags & DADD_TUNE_SHALLOW) != 0;   // A/B switch: measured equal to the one-wave build (see the kernel comment)
-  if (a.flags & DADD_PRE_GN) {
-    if (a.Wo == 64) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<64, false, true>", flop, bytes}, conv3x3_halo_kernel<64, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
-    else if (a.Wo == 32) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<32, false, true>", flop, bytes}, conv3x3_halo_kernel<32, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
-    else dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<16, false, true>", flop, bytes}, conv3x3_halo_kernel<16, false, true>, grid, dim3(512), SMEM_BYTES_GNIN, s, a);
-  } else if (duo) {
-    if (a.Wo == 64) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<64, true, false>", flop, bytes}, conv3x3_halo_kernel<64, true>, grid, dim3(768), SMEM_BYTES, s, a);
-    else if (a.Wo == 32) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<32, true, false>", flop, bytes}, conv3x3_halo_kernel<32, true>, grid, dim3(768), SMEM_BYTES, s, a);
-    else dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<16, true, false>", flop, bytes}, conv3x3_halo_kernel<16, true>, grid, dim3(768), SMEM_BYTES, s, a);
-  } else {
-    if (a.Wo == 64) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<64, false, false>", flop, bytes}, conv3x3_halo_kernel<64, false>, grid, dim3(512), SMEM_BYTES, s, a);
-    else if (a.Wo == 32) dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<32, false, false>", flop, bytes}, conv3x3_halo_kernel<32, false>, grid, dim3(512), SMEM_BYTES, s, a);
-    else dadd_launch({DADD_KNAME("conv3x3_halo_kernel") "<16, false, false>", flop, bytes}, conv3x3_halo_kernel<16, false>, grid, dim3(512), SMEM_BYTES, s, a);
-  }
-  DADD_LAUNCH_CHECK();
-  return DADD_OK;
 }

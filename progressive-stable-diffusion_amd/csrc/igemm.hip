@@ -418,49 +418,50 @@ __global__ __launch_bounds__(512) void splitk_finish_gnapply_kernel(const IgemmA
 
 constexpr double L2_KEEP = 3.0e6;   // bytes of one operand an XCD's 4 MB L2 can be trusted to keep while the other streams
 
-template <int BM, int BN, bool DEEP>
-int set_attr() {
-  constexpr int smem = 2 * (BM + BN) * BK * (int)sizeof(half_t) + (BM == 128 ? (BN == 160 ? 8192 : LN_LDS_BYTES) : 4096);
-  DADD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, DEEP>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  return DADD_OK;
+constexpr int smem_bytes(int bm, int bn) {   // two K-tile buffers + the epilogue's scratch
+  return 2 * (bm + bn) * BK * (int)sizeof(half_t) + (bm == 128 ? (bn == 160 ? 8192 : LN_LDS_BYTES) : 4096);
 }
 
-template <int BM, int BN, bool DEEP>
-int launch(const IgemmArgs& a, int nsplit, hipStream_t s) {
-  constexpr int smem = 2 * (BM + BN) * BK * (int)sizeof(half_t) + (BM == 128 ? (BN == 160 ? 8192 : LN_LDS_BYTES) : 4096);   // + the epilogue's scratch
-  const int mtiles = (a.M + BM - 1) / BM;
-  dim3 grid(mtiles * a.ntiles, nsplit);
-  static const std::string name = DADD_KNAME("igemm_kernel") "<" + std::to_string(BM) + ", " + std::to_string(BN) + ", " + (DEEP ? "true" : "false") + ">";
-  dadd_launch({name.c_str(), dadd_igemm_flop(a), dadd_igemm_bytes(a)}, igemm_kernel<BM, BN, DEEP>, grid, dim3(256), smem, s, a);
-  DADD_LAUNCH_CHECK();
-  return DADD_OK;
-}
+// kernel tables (igemm_args.h).  Register-staged kernel: BM, BN, DEEP — two K tiles in flight except where that spills (128x160)
+#define REG_ROW(BM, BN, DEEP) \
+  {DADD_KNAME("igemm_kernel") "<" #BM ", " #BN ", " #DEEP ">", igemm_kernel<BM, BN, DEEP>, 256, smem_bytes(BM, BN), {BM, BN, DEEP}}
+const IgemmKernel REG_KERNELS[] = {
+    REG_ROW(128, 128, false), REG_ROW(128, 128, true), REG_ROW(128, 160, false), REG_ROW(64, 128, false),
+    REG_ROW(64, 128, true),   REG_ROW(64, 160, false), REG_ROW(64, 160, true),
+};
+#undef REG_ROW
+// Finish kernels, keyed by their template arguments: GNAPPLY VEC | none | GNSTAT CB, R.  The gnapply rows take their
+// LDS (one (sample, group) slab) per launch.
+#define FIN_ROW(KERNEL, THREADS, ...) {DADD_KNAME(#KERNEL), KERNEL<__VA_ARGS__>, THREADS, 0, {__VA_ARGS__}}
+const IgemmFinish FINISH_KERNELS[] = {
+    FIN_ROW(splitk_finish_gnapply_kernel, 512, 4), FIN_ROW(splitk_finish_gnapply_kernel, 512, 2),
+    {DADD_KNAME("splitk_finish_kernel"), splitk_finish_kernel, 256, 0, {}},
+    FIN_ROW(splitk_finish_gn_kernel, 256, 160, 16), FIN_ROW(splitk_finish_gn_kernel, 256, 160, 64),
+    FIN_ROW(splitk_finish_gn_kernel, 256, 128, 16), FIN_ROW(splitk_finish_gn_kernel, 256, 128, 64),
+};
+#undef FIN_ROW
 
-template <int BM, int BN>
-int launch2(const IgemmArgs& a, int nsplit, bool deep, hipStream_t s) {
-  return deep ? launch<BM, BN, true>(a, nsplit, s) : launch<BM, BN, false>(a, nsplit, s);
-}
+int g_num_cu = 0;
 
 }  // namespace
 
 int dadd_init_igemm() {
   int rc = dadd_init_igemm_dma();
   if (rc == DADD_OK) rc = dadd_init_conv_halo();
-  if (rc == DADD_OK) rc = set_attr<128, 128, false>();
-  if (rc == DADD_OK) rc = set_attr<128, 128, true>();
-  if (rc == DADD_OK) rc = set_attr<128, 160, false>();
-  if (rc == DADD_OK) rc = set_attr<64, 128, false>();
-  if (rc == DADD_OK) rc = set_attr<64, 128, true>();
-  if (rc == DADD_OK) rc = set_attr<64, 160, false>();
-  if (rc == DADD_OK) rc = set_attr<64, 160, true>();
+  if (rc == DADD_OK) rc = dadd_set_max_lds(REG_KERNELS);
+  int dev = 0;
+  DADD_HIP(hipGetDevice(&dev));
+  DADD_HIP(hipDeviceGetAttribute(&g_num_cu, hipDeviceAttributeMultiprocessorCount, dev));
   return rc;
 }
 
-extern "C" int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream) {
+// Descriptor -> launch: decodes and validates `d` and decides everything a call launches — kernel (register-staged,
+// LDS-DMA, halo), tile order, K slicing, persistence, finish kernel — for a device with `num_cu` compute units.  Holds
+// every requirement of the three kernel files; touches neither the device nor the buffers.
+int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
   DADD_REQUIRE(d != nullptr, "igemm: null descriptor");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  IgemmArgs a;
+  IgemmArgs& a = out->a;
+  a = IgemmArgs{};
   a.x = static_cast<const half_t*>(d->x);
   a.x2 = static_cast<const half_t*>(d->x2);
   a.w = static_cast<const half_t*>(d->w);
@@ -580,7 +581,6 @@ extern "C" int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream) {
   // consecutive K tiles — measured no different: the DMA stream is bound by the L2->LDS fill rate of a CU, not by
   // L1 hits: profiles/r01_x_dma_limits.txt.)
   a.korder = 0;
-  int rc;
   // LDS-DMA ring kernel (igemm_dma.hip) for 128-row tiles; the register-staged kernel below keeps
   // the 64-row tiles and serves as the A/B reference (DADD_TUNE_NODMA)
   // (the 64-row LDS-DMA tiles have no upsample gather: such a request runs on the register-staged kernel; a folded
@@ -594,8 +594,10 @@ extern "C" int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream) {
   // Weight-heavy GEMMs (the GEGLU projection of the 16x16 map: 26 MB of weights against 2.6 MB of activations) keep
   // the grouped order: row tile fastest inside a group of column tiles, so the runs of neighbouring workgroups —
   // same XCD, started together — read each weight tile from HBM once instead of once per row tile.
-  if (dma && tile_m == 128 && dadd_igemm_dma_persistent(a, nsplit) &&
-      ((d->flags & DADD_TUNE_SHALLOW) ? false : 2.0 * a.B * a.Hi * a.Wi * Cin >= 2.0 * a.N * a.K))
+  // (128-row tiles, more tiles than CUs, no split-K, no upsample gather)
+  const bool persistent = dma && tile_m == 128 && (a.flags & DADD_TUNE_PERSIST) && nsplit == 1 && !a.ups && num_cu > 0 &&
+                          a.mtiles * a.ntiles > num_cu;
+  if (persistent && ((d->flags & DADD_TUNE_SHALLOW) ? false : 2.0 * a.B * a.Hi * a.Wi * Cin >= 2.0 * a.N * a.K))
     a.gm = a.gn = 0;
   // 3x3 / stride 1 on whole-row tiles: the halo-resident kernel (conv_halo.hip); K slices = channel chunks
   const bool halo = dma && tile_m == 128 && dadd_conv_halo_applicable(a, tile_n);
@@ -657,44 +659,75 @@ extern "C" int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream) {
   } else {
     DADD_REQUIRE(!(a.flags & DADD_PRE_GN_SILU), "igemm: DADD_PRE_GN_SILU without DADD_PRE_GN");
   }
+  // buffer offsets of the LDS-DMA kernels are 32-bit with bit 31 reserved as the out-of-range marker
+  const bool window = (size_t)a.B * a.Hi * a.Wi * (size_t)(a.C1 > a.C2 ? a.C1 : a.C2) * 2 < 0x7FF00000ull &&
+                      (size_t)a.N * a.K * 2 < 0x7FF00000ull;
+  out->nsplit = halo ? halo_ns : nsplit;
+  out->tile_m = tile_m;
+  out->tile_n = tile_n;
+  out->persistent = !halo && persistent;
+  out->grid = out->persistent ? dim3(num_cu) : dim3(a.mtiles * a.ntiles, out->nsplit);
   if (halo) {
-    if (d->flags & DADD_TUNE_SHALLOW) a.flags |= DADD_TUNE_SHALLOW;   // A/B: the two-MFMA-waves-per-SIMD build
-    rc = dadd_launch_conv_halo(a, halo_ns, s);
+    DADD_REQUIRE(window, "conv_halo: operand larger than the 2 GiB buffer window");
+    const bool duo = (d->flags & DADD_TUNE_SHALLOW) != 0 && !(a.flags & DADD_PRE_GN);   // A/B: the two-MFMA-waves-per-SIMD build
+    if (d->flags & DADD_TUNE_SHALLOW) a.flags |= DADD_TUNE_SHALLOW;
+    out->main = dadd_conv_halo_row(a.Wo, duo, (a.flags & DADD_PRE_GN) != 0);
+  } else if (dma) {
+    DADD_REQUIRE(window, "igemm(dma): operand larger than the 2 GiB buffer window");
+    DADD_REQUIRE(tile_m == 128 || !a.ups, "igemm(dma): the 64-row tiles have no upsample gather");
+    // how a folded LayerNorm gets its row statistics (LNK, igemm_dma.hip): 1 the kernel sums the rows itself, 2 (128-row
+    // tiles) the producer's partials staged in LDS, 0 no fold or the epilogue reads the partials from global memory
+    const int lnk = (a.ups || !(a.flags & DADD_EPI_LNFOLD)) ? 0 : (a.ln_stats_in == nullptr ? 1 : (tile_m == 128 ? 2 : 0));
+    out->main = dadd_igemm_dma_row(tile_m, tile_n, !out->persistent && tile_m == 128 && a.ups, out->persistent, lnk);
+  } else {
+    out->main = dadd_find_row(REG_KERNELS, tile_m, tile_n, deep && !(tile_m == 128 && tile_n == 160));
   }
-  else if (dma)
-    rc = dadd_launch_igemm_dma(a, tile_m, tile_n, nsplit, s);
-  else if (tile_m == 128)
-    rc = (tile_n == 160) ? launch<128, 160, false>(a, nsplit, s) : launch2<128, 128>(a, nsplit, deep, s);
-  else
-    rc = (tile_n == 160) ? launch2<64, 160>(a, nsplit, deep, s) : launch2<64, 128>(a, nsplit, deep, s);
-  if (rc != DADD_OK) return rc;
-  if ((halo ? halo_ns : nsplit) > 1 && a.counters == nullptr) {
-    const size_t total = (size_t)a.M * (a.N / 4);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    const int ns = halo ? halo_ns : nsplit;
-    const DaddLaunchTag tag = {(a.flags & DADD_EPI_GNSTAT) ? DADD_KNAME("splitk_finish_gn_kernel") : DADD_KNAME("splitk_finish_kernel"), 0.0,
-                               (double)a.M * a.N * (4.0 * ns + 2.0 + ((a.flags & DADD_EPI_RESIDUAL) ? 2.0 : 0.0))};
+  DADD_REQUIRE(out->main != nullptr, "igemm: no kernel for %d x %d tiles", tile_m, tile_n);
+  out->finish = nullptr;
+  out->fgrid = dim3(0);
+  out->fsmem = 0;
+  if (out->nsplit > 1 && a.counters == nullptr) {
     if (a.flags & DADD_EPI_GNAPPLY) {
-      const DaddLaunchTag tag2 = {DADD_KNAME("splitk_finish_gnapply_kernel"), 0.0, tag.bytes + 2.0 * a.M * a.N};
-      const unsigned slab_bytes = (unsigned)(a.Ho * a.Wo * (a.N / 32) * 2);
-      if ((a.N / 32) % 4 == 0 && a.ldo % 4 == 0 && a.ldr % 4 == 0 && a.ld_rowvec % 4 == 0)
-        dadd_launch(tag2, splitk_finish_gnapply_kernel<4>, dim3(32, a.B), dim3(512), slab_bytes, s, a, ns);
-      else
-        dadd_launch(tag2, splitk_finish_gnapply_kernel<2>, dim3(32, a.B), dim3(512), slab_bytes, s, a, ns);
-    } else if (!(a.flags & DADD_EPI_GNSTAT))
-      dadd_launch(tag, splitk_finish_kernel, dim3(blocks), dim3(256), 0, s, a, ns);
-    else {
-      const int rows = (a.Ho * a.Wo) / a.gn_nchunk;
-      if (a.N % 160 == 0) {
-        if (rows == 16) dadd_launch(tag, splitk_finish_gn_kernel<160, 16>, dim3(a.M / 16, a.N / 160), dim3(256), 0, s, a, ns);
-        else dadd_launch(tag, splitk_finish_gn_kernel<160, 64>, dim3(a.M / 64, a.N / 160), dim3(256), 0, s, a, ns);
-      } else {
-        if (rows == 16) dadd_launch(tag, splitk_finish_gn_kernel<128, 16>, dim3(a.M / 16, a.N / 128), dim3(256), 0, s, a, ns);
-        else dadd_launch(tag, splitk_finish_gn_kernel<128, 64>, dim3(a.M / 64, a.N / 128), dim3(256), 0, s, a, ns);
-      }
+      const bool vec4 = (a.N / 32) % 4 == 0 && a.ldo % 4 == 0 && a.ldr % 4 == 0 && a.ld_rowvec % 4 == 0;
+      out->finish = dadd_find_row(FINISH_KERNELS, vec4 ? 4 : 2);
+      out->fgrid = dim3(32, a.B);
+      out->fsmem = (unsigned)(a.Ho * a.Wo * (a.N / 32) * 2);
+    } else if (!(a.flags & DADD_EPI_GNSTAT)) {
+      const size_t total = (size_t)a.M * (a.N / 4);
+      const int blocks = (int)((total + 255) / 256);
+      out->finish = dadd_find_row(FINISH_KERNELS, 0);
+      out->fgrid = dim3(blocks > 2048 ? 2048 : blocks);
+    } else {
+      const int cb = (a.N % 160 == 0) ? 160 : 128, rows = (a.Ho * a.Wo) / a.gn_nchunk == 16 ? 16 : 64;
+      out->finish = dadd_find_row(FINISH_KERNELS, cb, rows);
+      out->fgrid = dim3(a.M / rows, a.N / cb);
     }
-    DADD_LAUNCH_CHECK();
   }
+  return DADD_OK;
+}
+
+extern "C" int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  IgemmLaunch l;
+  const int rc = dadd_igemm_resolve(d, g_num_cu, &l);
+  if (rc != DADD_OK) return rc;
+  const IgemmArgs& a = l.a;
+  dadd_launch({l.main->name, dadd_igemm_flop(a), dadd_igemm_bytes(a)}, l.main->fn, l.grid, dim3(l.main->threads), l.main->smem, s, a);
+  if (l.finish) {
+    double bytes = (double)a.M * a.N * (4.0 * l.nsplit + 2.0 + ((a.flags & DADD_EPI_RESIDUAL) ? 2.0 : 0.0));
+    if (a.flags & DADD_EPI_GNAPPLY) bytes += 2.0 * a.M * a.N;
+    dadd_launch({l.finish->name, 0.0, bytes}, l.finish->fn, l.fgrid, dim3(l.finish->threads), l.fsmem, s, a, l.nsplit);
+  }
+  DADD_LAUNCH_CHECK();
+  return DADD_OK;
+}
+
+extern "C" int dadd_conv_igemm_resolve_f16(const dadd_igemm_desc* d, int num_cu, dadd_igemm_choice* out) {
+  DADD_REQUIRE(out != nullptr, "igemm: null choice");
+  IgemmLaunch l;
+  const int rc = dadd_igemm_resolve(d, num_cu, &l);
+  if (rc != DADD_OK) return rc;
+  *out = {l.main->name, l.finish ? l.finish->name : nullptr, l.tile_m, l.tile_n, l.nsplit, l.a.kps, l.persistent,
+          (int)l.grid.x, (int)l.grid.y, l.main->threads, l.main->smem, l.a.gm, l.a.gn};
   return DADD_OK;
 }

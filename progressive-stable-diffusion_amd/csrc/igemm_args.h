@@ -121,10 +121,51 @@ __device__ __forceinline__ void ln_finish(float (&s1)[MI], float (&s2)[MI], int 
   }
 }
 
+// ---- kernel table, resolve, launch ------------------------------------------------------------------------------
+// Every kernel instantiation of igemm.hip, igemm_dma.hip and conv_halo.hip is ONE row of its file's table: the name
+// the profiler shows, the kernel, threads per block, dynamic LDS bytes, and the template arguments it was made from
+// (`targ`, the lookup key).  The row macros build the name from the same arguments as the template-id.  dadd_init_*
+// loops over a table for the LDS attribute; dadd_igemm_resolve (igemm.hip) picks rows; nothing else names a kernel.
+template <typename... A>
+struct KernelRow {
+  const char* name;
+  void (*fn)(A...);
+  int threads, smem;
+  int targ[5];
+};
+typedef KernelRow<IgemmArgs> IgemmKernel;         // the GEMM / conv kernels: void(const IgemmArgs)
+typedef KernelRow<IgemmArgs, int> IgemmFinish;    // the split-K finish kernels: void(const IgemmArgs, int nsplit)
+
+template <typename Row, int N>
+inline const Row* dadd_find_row(const Row (&rows)[N], int k0, int k1 = 0, int k2 = 0, int k3 = 0, int k4 = 0) {
+  for (const Row& r : rows)
+    if (r.targ[0] == k0 && r.targ[1] == k1 && r.targ[2] == k2 && r.targ[3] == k3 && r.targ[4] == k4) return &r;
+  return nullptr;
+}
+template <typename Row, int N>
+inline int dadd_set_max_lds(const Row (&rows)[N]) {
+  for (const Row& r : rows)
+    DADD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, r.smem));
+  return DADD_OK;
+}
+
+// What one dadd_conv_igemm_f16 call launches, decided by dadd_igemm_resolve without touching the device.
+struct IgemmLaunch {
+  IgemmArgs a;
+  const IgemmKernel* main;
+  dim3 grid;
+  const IgemmFinish* finish;   // nullptr: no finish launch (one K slice, or the slabs are combined by tickets)
+  dim3 fgrid;
+  unsigned fsmem;
+  int nsplit;                  // K slices of the main launch (grid.y)
+  int tile_m, tile_n;
+  bool persistent;
+};
+int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out);
+
 int dadd_init_igemm_dma();
-int dadd_launch_igemm_dma(const IgemmArgs& a, int tile_m, int tile_n, int nsplit, hipStream_t s);
-bool dadd_igemm_dma_persistent(const IgemmArgs& a, int nsplit);
+const IgemmKernel* dadd_igemm_dma_row(int tile_m, int tile_n, bool ups, bool persistent, int lnk);
 int dadd_init_conv_halo();
 bool dadd_conv_halo_applicable(const IgemmArgs& a, int tile_n);
 int dadd_conv_halo_gn_channels(int Wo);
-int dadd_launch_conv_halo(const IgemmArgs& a, int nsplit, hipStream_t s);   // a.kps = chunks per K slice
+const IgemmKernel* dadd_conv_halo_row(int Wo, bool duo, bool gn_in);

@@ -397,102 +397,31 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
 #endif
 }
 
-template <int BM, int BN>
-constexpr int smem_bytes() {   // ring + the epilogue's scratch (GroupNorm partials; 128-row tiles: the staged LayerNorm operands)
-  return 4 * (BM + BN) * BK * 2 + (BM == 128 ? LN_LDS_BYTES : 4096);
+constexpr int smem_bytes(int bm, int bn) {   // ring + the epilogue's scratch (GroupNorm partials; 128-row tiles: the staged LayerNorm operands)
+  return 4 * (bm + bn) * BK * 2 + (bm == 128 ? LN_LDS_BYTES : 4096);
 }
 
-template <int BM, int BN, bool UPS, bool PERS, int LNK>
-int set_attr() {
-  DADD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_dma_kernel<BM, BN, UPS, PERS, LNK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes<BM, BN>()));
-  return DADD_OK;
-}
-
-int g_num_cu = 0;
-
-template <int BM, int BN, bool UPS, bool PERS, int LNK>
-void launch1(const char* name, const IgemmArgs& a, dim3 grid, hipStream_t s) {
-  dadd_launch({name, dadd_igemm_flop(a), dadd_igemm_bytes(a)}, igemm_dma_kernel<BM, BN, UPS, PERS, LNK>, grid, dim3(512),
-              smem_bytes<BM, BN>(), s, a);
-}
-// plain linears / convs and (no upsample) their LayerNorm-folded twins; `names`: kernel name per LNK (profiling records)
-template <int BM, int BN, bool UPS, bool PERS>
-void launch(const char* const (&names)[3], const IgemmArgs& a, dim3 grid, hipStream_t s) {
-  if constexpr (!UPS) {
-    if ((a.flags & DADD_EPI_LNFOLD) && a.ln_stats_in == nullptr) {     // the kernel sums the rows itself
-      launch1<BM, BN, false, PERS, 1>(names[1], a, grid, s);
-      return;
-    }
-    if constexpr (BM == 128) {
-      if (a.flags & DADD_EPI_LNFOLD) {                                   // the producer's partials, staged in LDS
-        launch1<BM, BN, false, PERS, 2>(names[2], a, grid, s);
-        return;
-      }
-    }
-  }
-  launch1<BM, BN, UPS, PERS, 0>(names[0], a, grid, s);
-}
-template <int BM, int BN, bool PERS>
-int set_attr2() {
-  int rc = set_attr<BM, BN, false, PERS, 0>();
-  if (rc == DADD_OK) rc = set_attr<BM, BN, false, PERS, 1>();
-  if constexpr (BM == 128) {
-    if (rc == DADD_OK) rc = set_attr<BM, BN, false, PERS, 2>();
-  }
-  return rc;
-}
+// kernel table (igemm_args.h): BM, BN, UPS, PERS, LNK.  Plain linears / convs and (no upsample) their LayerNorm-folded
+// twins; LNK 2 exists on the 128-row tiles only.
+#define DMA_ROW(BM, BN, UPS, PERS, LNK)                                                                                \
+  {DADD_KNAME("igemm_dma_kernel") "<" #BM ", " #BN ", " #UPS ", " #PERS ", " #LNK ">", igemm_dma_kernel<BM, BN, UPS, PERS, LNK>, \
+   512, smem_bytes(BM, BN), {BM, BN, UPS, PERS, LNK}}
+#define DMA_ROWS2(BM, BN, PERS) DMA_ROW(BM, BN, false, PERS, 0), DMA_ROW(BM, BN, false, PERS, 1)
+#define DMA_ROWS3(BM, BN, PERS) DMA_ROWS2(BM, BN, PERS), DMA_ROW(BM, BN, false, PERS, 2)
+const IgemmKernel DMA_KERNELS[] = {
+    DMA_ROWS3(128, 128, true),  DMA_ROWS3(128, 160, true),
+    DMA_ROWS3(128, 128, false), DMA_ROWS3(128, 160, false),
+    DMA_ROW(128, 128, true, false, 0), DMA_ROW(128, 160, true, false, 0),
+    DMA_ROWS2(64, 64, false), DMA_ROWS2(64, 128, false), DMA_ROWS2(64, 160, false),
+};
+#undef DMA_ROWS3
+#undef DMA_ROWS2
+#undef DMA_ROW
 
 }  // namespace
 
-int dadd_init_igemm_dma() {
-  int rc = set_attr2<128, 128, true>();
-  if (rc == DADD_OK) rc = set_attr2<128, 160, true>();
-  if (rc == DADD_OK) rc = set_attr2<128, 128, false>();
-  if (rc == DADD_OK) rc = set_attr2<128, 160, false>();
-  if (rc == DADD_OK) rc = set_attr<128, 128, true, false, 0>();
-  if (rc == DADD_OK) rc = set_attr<128, 160, true, false, 0>();
-  if (rc == DADD_OK) rc = set_attr2<64, 64, false>();
-  if (rc == DADD_OK) rc = set_attr2<64, 128, false>();
-  if (rc == DADD_OK) rc = set_attr2<64, 160, false>();
-  int dev = 0;
-  DADD_HIP(hipGetDevice(&dev));
-  DADD_HIP(hipDeviceGetAttribute(&g_num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  return rc;
-}
+int dadd_init_igemm_dma() { return dadd_set_max_lds(DMA_KERNELS); }
 
-// persistent ring over several output tiles: 128-row tiles, more tiles than CUs, no split-K, no upsample gather
-bool dadd_igemm_dma_persistent(const IgemmArgs& a, int nsplit) {
-  return (a.flags & DADD_TUNE_PERSIST) && nsplit == 1 && !a.ups && g_num_cu > 0 && a.mtiles * a.ntiles > g_num_cu;
-}
-
-// `a.mtiles` / `a.ntiles` are the tile counts for (tile_m, tile_n), set by the caller
-int dadd_launch_igemm_dma(const IgemmArgs& a, int tile_m, int tile_n, int nsplit, hipStream_t s) {
-  const int total = a.mtiles * a.ntiles;
-  // buffer offsets are 32-bit with bit 31 reserved as the out-of-range marker
-  DADD_REQUIRE((size_t)a.B * a.Hi * a.Wi * (size_t)(a.C1 > a.C2 ? a.C1 : a.C2) * 2 < 0x7FF00000ull &&
-                   (size_t)a.N * a.K * 2 < 0x7FF00000ull,
-               "igemm(dma): operand larger than the 2 GiB buffer window");
-  if (tile_m == 128 && dadd_igemm_dma_persistent(a, nsplit)) {
-    dim3 grid(g_num_cu);
-    if (tile_n == 160) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 160, false, true, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, true, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, true, 2>"}; launch<128, 160, false, true>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 128, false, true, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, true, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, true, 2>"}; launch<128, 128, false, true>(nm, a, grid, s); }
-    DADD_LAUNCH_CHECK();
-    return DADD_OK;
-  }
-  dim3 grid(total, nsplit);
-  if (tile_m == 64) {
-    DADD_REQUIRE(!a.ups, "igemm(dma): the 64-row tiles have no upsample gather");
-    if (tile_n == 160) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<64, 160, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<64, 160, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<64, 160, false, false, 2>"}; launch<64, 160, false, false>(nm, a, grid, s); }
-    else if (tile_n == 128) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<64, 128, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<64, 128, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<64, 128, false, false, 2>"}; launch<64, 128, false, false>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<64, 64, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<64, 64, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<64, 64, false, false, 2>"}; launch<64, 64, false, false>(nm, a, grid, s); }
-  } else if (tile_n == 160) {
-    if (a.ups) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 160, true, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 160, true, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 160, true, false, 2>"}; launch<128, 160, true, false>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 160, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 160, false, false, 2>"}; launch<128, 160, false, false>(nm, a, grid, s); }
-  } else {
-    if (a.ups) { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 128, true, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 128, true, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 128, true, false, 2>"}; launch<128, 128, true, false>(nm, a, grid, s); }
-    else { static const char* const nm[3] = {DADD_KNAME("igemm_dma_kernel") "<128, 128, false, false, 0>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, false, 1>", DADD_KNAME("igemm_dma_kernel") "<128, 128, false, false, 2>"}; launch<128, 128, false, false>(nm, a, grid, s); }
-  }
-  DADD_LAUNCH_CHECK();
-  return DADD_OK;
+const IgemmKernel* dadd_igemm_dma_row(int tile_m, int tile_n, bool ups, bool persistent, int lnk) {
+  return dadd_find_row(DMA_KERNELS, tile_m, tile_n, ups, persistent, lnk);
 }

@@ -44,6 +44,13 @@ class IgemmDesc(C.Structure):
                                                            ("gn_out", vp), ("gn_out_gamma", vp), ("gn_out_beta", vp), ("gn_out_eps", f32)]
 
 
+class IgemmChoice(C.Structure):
+    """Mirror of ``dadd_igemm_choice``: what ``dadd_conv_igemm_*`` would launch for a descriptor."""
+    _fields_ = [("kernel", C.c_char_p), ("finish", C.c_char_p)] + \
+               [(n, i32) for n in ("tile_m", "tile_n", "nsplit", "kps", "persistent", "grid_x", "grid_y", "block", "smem",
+                                   "gm", "gn")]
+
+
 class WgradDesc(C.Structure):
     """Mirror of ``dadd_wgrad_desc``."""
     _fields_ = [(n, vp) for n in ("dy", "x", "dw", "dbias", "partial")] + \
@@ -58,6 +65,7 @@ PROTOTYPES = {
     "dadd_init": (C.c_int, []),
     "dadd_device_info": (C.c_int, [C.c_int, C.POINTER(i64)]),
     "dadd_conv_igemm_f16": (C.c_int, [C.POINTER(IgemmDesc), vp]),
+    "dadd_conv_igemm_resolve_f16": (C.c_int, [C.POINTER(IgemmDesc), C.c_int, C.POINTER(IgemmChoice)]),
     "dadd_conv3x3_cin8_f16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "dadd_conv_in_nchw_f16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "dadd_conv3x3_cout4_f16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -116,6 +124,11 @@ PROTOTYPES = {
     "dadd_prof_record": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double)]),
 }
 
+# every symbol include/dadd_hip_host.h declares (host-only: what a descriptor would launch, csrc/igemm.hip resolve)
+HOST_PROTOTYPES = {
+    "dadd_conv_igemm_resolve_bf16": (C.c_int, [C.POINTER(IgemmDesc), C.c_int, C.POINTER(IgemmChoice)]),
+}
+
 # every symbol include/dadd_hip_grad.h declares (training backward only)
 GRAD_PROTOTYPES = {
     "dadd_conv_wgrad_bf16": (C.c_int, [C.POINTER(WgradDesc), vp]),
@@ -129,7 +142,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
-        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h")]
+        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -155,7 +168,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension is required (run __graft_entry__.build()); "
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **GRAD_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

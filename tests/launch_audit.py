@@ -35,6 +35,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from progressive_stable_diffusion_amd.lib import (EPI_GEGLU, EPI_GELU, EPI_GNAPPLY_SILU, EPI_LNFOLD, EPI_QUICKGELU, EPI_SIGMOID,
+                                                 PRE_GN)
 from tests import attention_cases as AC
 from tests.torch_backend import TorchRefBackend
 
@@ -48,8 +50,7 @@ REPORT_ABOVE = 1.1
 # reference of conv_in_nchw rounds the latents to the plan's storage type as the kernel does (bf16 plans: 1.43 before).
 REASONS = {}
 
-EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
-EPI_LNFOLD, EPI_ACT, EPI_GNSTAT, EPI_LNSTAT, PRE_GN, EPI_GNAPPLY = 128, 256 | 512 | 1024, 2048, 4096, 8192, 32768
+EPI_ACT = EPI_QUICKGELU | EPI_GELU | EPI_SIGMOID
 NONLINEAR = EPI_GEGLU | EPI_LNFOLD | EPI_ACT | PRE_GN
 
 # (dtype, key) -> (atol, rtol, the test the pair comes from).  One place; nothing else in the audit holds a tolerance.
@@ -377,7 +378,7 @@ class AuditBackend:
                 self._record("igemm", "gn_ws", sig, a["gn_ws"][:want.numel()].reshape(want.shape), want, bound, None, t0)
             if a["gn_apply"] is not None:           # GroupNorm (+ SiLU) of the stored output, written beside it
                 g_out, gam, bet, eps_o = a["gn_apply"]
-                silu = bool(flags & 65536)
+                silu = bool(flags & EPI_GNAPPLY_SILU)
                 g64, g32 = torch.zeros(g_out.shape, dtype=F64, device=g_out.device), torch.zeros_like(g_out)
                 self.ref64.groupnorm(o, None, gam, bet, g64, None, 32, eps_o, silu)
                 self.ref32.groupnorm(o, None, gam, bet, g32, None, 32, eps_o, silu)

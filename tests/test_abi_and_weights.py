@@ -51,6 +51,49 @@ def test_igemm_desc_layout_matches_header(tmp_path):
     assert [getattr(L.IgemmDesc, f).offset for f in fields] == out[1:]
 
 
+def _c_program_output(tmp_path, body):
+    """The integers a C program that includes include/dadd_hip.h prints, one per line of ``body``."""
+    import subprocess
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dadd_hip.h"\nint main(void) {\n' + body + "  return 0;\n}\n")
+    exe = tmp_path / "probe"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    return [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+
+
+def test_igemm_choice_layout_matches_header(tmp_path):
+    """... and the mirror of ``dadd_igemm_choice`` (what the resolve entry points fill), the same way."""
+    fields = [f[0] for f in L.IgemmChoice._fields_]
+    assert fields[:2] == ["kernel", "finish"]
+    out = _c_program_output(tmp_path, '  printf("%zu\\n", sizeof(dadd_igemm_choice));\n'
+                            + "".join(f'  printf("%zu\\n", offsetof(dadd_igemm_choice, {f}));\n' for f in fields))
+    assert ctypes.sizeof(L.IgemmChoice) == out[0]
+    assert [getattr(L.IgemmChoice, f).offset for f in fields] == out[1:]
+
+
+def test_host_entry_points_are_declared_exported_and_bound():
+    """The bf16 sibling of the resolve entry point: include/dadd_hip_host.h and ``lib.HOST_PROTOTYPES``, same argument
+    list as the fp16 form of include/dadd_hip.h."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dadd_hip_host.h")).read(), flags=re.S)
+    assert set(re.findall(r"\b(dadd_[a-z0-9_]+)\s*\(", text)) == set(L.HOST_PROTOTYPES) == {"dadd_conv_igemm_resolve_bf16"}
+    assert L.HOST_PROTOTYPES["dadd_conv_igemm_resolve_bf16"] == L.PROTOTYPES["dadd_conv_igemm_resolve_f16"]
+    assert L.PROTOTYPES["dadd_conv_igemm_resolve_f16"][1][2]._type_ is L.IgemmChoice
+    handle = ctypes.CDLL(L.build())
+    assert hasattr(handle, "dadd_conv_igemm_resolve_bf16")
+
+
+def test_flag_constants_match_header(tmp_path):
+    """Every EPI_* / PRE_* / TUNE_* constant of lib.py against the header's #define of the same name, through the C
+    compiler; and the header defines no such flag that lib.py lacks."""
+    names = sorted(n for n in vars(L) if re.match(r"(EPI|PRE|TUNE)_[A-Z0-9_]+$", n))
+    assert len(names) >= 17
+    header = re.findall(r"#define\s+DADD_((?:EPI|PRE|TUNE)_[A-Z0-9_]+)\b", open(os.path.join(ROOT, "include", "dadd_hip.h")).read())
+    assert set(header) - {"EPI_ACT_MASK"} == set(names), set(header) ^ set(names)
+    out = _c_program_output(tmp_path, "".join(f'  printf("%d\\n", DADD_{n});\n' for n in names))
+    assert out == [getattr(L, n) for n in names]
+    assert _c_program_output(tmp_path, '  printf("%d\\n", DADD_EPI_ACT_MASK);\n') == [L.EPI_QUICKGELU | L.EPI_GELU | L.EPI_SIGMOID]
+
+
 def test_status_codes_map_to_reference_exceptions():
     L.load()
     L.check(0)

@@ -1133,3 +1133,98 @@ def test_frames_to_u8_contract(hip):
     x = dev(hip, torch.rand(1, 3, 3, 3))
     with pytest.raises(ValueError, match="multiple of 4"):
         hip.frames_to_u8(x, hip.zeros((1, 3, 3, 3), torch.uint8))
+
+
+RESOLVE_FAMILIES = ["reg64x128", "reg128x160", "dma64x64", "dma128x160", "lnfold_own_rows", "lnfold_stats_in", "ups", "persistent",
+                    "halo", "halo_pre_gn", "halo_splitk_finish", "finish_gnstat", "finish_gnapply"]
+
+
+@pytest.mark.parametrize("family", RESOLVE_FAMILIES)
+def test_igemm_resolve_names_what_launches(hip, family):
+    """``dadd_conv_igemm_resolve_f16`` against the launch itself: one eager launch per dispatch family of csrc/igemm.hip,
+    each at the smallest shape that reaches it, between prof_begin() and prof_end().  The recorded kernel names must be
+    [choice.kernel] or [choice.kernel, choice.finish] of the same descriptor resolved with the device's CU count, and the
+    output is compared with the torch reference at the tolerance of the family's own test above."""
+    import ctypes as C
+    from progressive_stable_diffusion_amd import lib as L
+    from progressive_stable_diffusion_amd.backend import _p, fill_igemm_desc
+    ncu = torch.cuda.get_device_properties(DEV).multi_processor_count
+    tol, kw, ref_kw, host, expect = (3e-3, 2e-3), {}, {}, {}, ""
+    lin = lambda m, n, k: (rnd((1, m, 1, k), 100), rnd((n, k), 101, 1 / math.sqrt(k)), (1, m, 1, n))      # noqa: E731
+    conv = lambda b, h, c, n, ho: (rnd((b, h, h, c), 100), rnd((n, 9 * c), 101, 1 / math.sqrt(9 * c)), (b, ho, ho, n))   # noqa: E731
+    if family == "reg64x128":
+        (x, w, osh), kw, expect = lin(100, 256, 128), dict(flags=L.TUNE_NODMA, tile_m=64, tile_n=128), "igemm_kernel<64, 128, true>"
+    elif family == "reg128x160":
+        (x, w, osh), kw, expect = lin(200, 320, 128), dict(flags=L.TUNE_NODMA, tile_m=128, tile_n=160), "igemm_kernel<128, 160, false>"
+    elif family == "dma64x64":
+        (x, w, osh), kw, expect = lin(100, 192, 128), dict(tile_m=64, tile_n=64), "igemm_dma_kernel<64, 64, false, false, 0>"
+    elif family == "dma128x160":
+        (x, w, osh), kw, expect = lin(200, 320, 128), dict(tile_m=128, tile_n=160), "igemm_dma_kernel<128, 160, false, false, 0>"
+    elif family in ("lnfold_own_rows", "lnfold_stats_in"):
+        (x, w, osh), tol = lin(200, 320, 128), (6e-3, 6e-3)
+        x = (x.float() + 2.0 * rnd((1, 200, 1, 1), 102).float()).to(F16)
+        host = dict(bias=rnd((320,), 103, 0.1, F32), ln_c1=w.float().sum(-1).contiguous())
+        kw = dict(flags=L.EPI_BIAS | L.EPI_LNFOLD, tile_m=128, tile_n=160)
+        expect = "igemm_dma_kernel<128, 160, false, false, 1>"
+        if family == "lnfold_stats_in":       # the row partials of x over its two 64-column blocks, as a producer writes them
+            xp = x.float().reshape(200, 2, 64)
+            host["ln_stats_in"] = torch.stack([xp.sum(-1), (xp * xp).sum(-1)], dim=-1).permute(1, 0, 2).contiguous()
+            expect = "igemm_dma_kernel<128, 160, false, false, 2>"
+    elif family == "ups":
+        (x, w, osh), kw = conv(1, 8, 64, 160, 16), dict(taps=9, pad=1, ups=1, tile_m=128, tile_n=160)
+        expect = "igemm_dma_kernel<128, 160, true, false, 0>"
+    elif family == "persistent":              # two more tiles than CUs
+        (x, w, osh), tol = lin(128 * (ncu // 2 + 1), 320, 64), (3e-3, 3e-3)
+        kw, expect = dict(flags=L.TUNE_PERSIST, tile_m=128, tile_n=160), "igemm_dma_kernel<128, 160, false, true, 0>"
+    elif family == "halo":
+        (x, w, osh), kw, expect = conv(1, 16, 64, 160, 16), dict(taps=9, pad=1, tile_m=128, tile_n=160), "conv3x3_halo_kernel<16, false, false>"
+    elif family == "halo_pre_gn":
+        (x, w, osh), tol = conv(1, 16, 64, 160, 16), (2e-3, 1e-3)
+        x = (x.float() * 1.7 + 0.6).to(F16)
+        xc = x.float().reshape(1, 4, -1, 32, 2)
+        part = torch.stack([xc.sum(dim=(2, 4)), (xc * xc).sum(dim=(2, 4))], dim=-1).contiguous().reshape(-1)
+        host = dict(gn_in=(part, 4, rnd((64,), 104, 0.2, F32) + 1.0, rnd((64,), 105, 0.2, F32), 1e-5))
+        kw, expect = dict(taps=9, pad=1, flags=L.PRE_GN, tile_m=128, tile_n=160), "conv3x3_halo_kernel<16, false, true>"
+    elif family == "halo_splitk_finish":
+        (x, w, osh), kw, expect = conv(1, 16, 128, 160, 16), dict(taps=9, pad=1, tile_m=128, tile_n=160, splitk=2), "conv3x3_halo_kernel<16, false, false>"
+    elif family == "finish_gnstat":           # 16-row chunks
+        x, w, osh = rnd((1, 16, 16, 128), 100), rnd((320, 128), 101, 1 / math.sqrt(128)), (1, 16, 16, 320)
+        kw, expect = dict(flags=L.EPI_GNSTAT, tile_m=128, tile_n=160, splitk=2, gn_nchunk=16), "igemm_dma_kernel<128, 160, false, false, 0>"
+        host = dict(gn_ws=torch.zeros(16 * 64))
+    else:
+        (x, w, osh), kw, expect = conv(1, 8, 64, 128, 8), dict(taps=9, pad=1, flags=L.EPI_GNAPPLY, splitk=3), "igemm_dma_kernel<128, 128, false, false, 0>"
+        host = dict(gn_apply=(torch.zeros(osh, dtype=F16), rnd((128,), 106, 0.1, F32) + 1.0, rnd((128,), 107, 0.1, F32), 1e-5))
+    m, n = osh[0] * osh[1] * osh[2], w.shape[0]
+    onh = {k: tuple(dev(hip, t) if isinstance(t, torch.Tensor) else t for t in v) if isinstance(v, tuple) else dev(hip, v)
+           for k, v in host.items()}
+    if kw.get("splitk", 1) > 1:
+        onh["partial"] = hip.zeros((kw["splitk"] * m * n,), F32)
+    xd, wd, o = dev(hip, x), dev(hip, w), hip.zeros(osh, F16)
+    d, ch = L.IgemmDesc(), L.IgemmChoice()
+    fill_igemm_desc(d, _p, xd, wd, o, **kw, **onh)
+    L.check(hip.lib.dadd_conv_igemm_resolve_f16(C.byref(d), ncu, C.byref(ch)))
+    want = [ch.kernel.decode()] + ([ch.finish.decode()] if ch.finish else [])
+    assert want[0] == expect and len(want) == (2 if kw.get("splitk", 1) > 1 else 1), want
+    assert bool(ch.persistent) == (family == "persistent") and (ch.grid_x == ncu or not ch.persistent)
+    hip.synchronize()
+    hip.prof_begin()
+    try:
+        hip.igemm(xd, wd, o, **kw, **onh)
+    finally:
+        rec = hip.prof_end()
+    hip.synchronize()
+    assert [r[0] for r in rec] == want, (family, rec, want)
+    o_ref = torch.zeros(osh, dtype=F16)
+    rkw = {k: v for k, v in kw.items() if k not in ("splitk", "tile_m", "tile_n")}
+    if family == "finish_gnapply":
+        y_ref = torch.zeros(osh, dtype=F16)
+        REF.igemm(x, w, o_ref, **rkw, gn_apply=(y_ref,) + host["gn_apply"][1:])
+        close(onh["gn_apply"][0], y_ref, 6e-3, 6e-3, f"{family}: normalised")
+    elif family == "finish_gnstat":
+        REF.igemm(x, w, o_ref, **{**rkw, "flags": 0})
+        oc = o.float().cpu().reshape(1, 16, 16, 32, 10)
+        part = torch.stack([oc.sum(dim=(2, 4)), (oc * oc).sum(dim=(2, 4))], dim=-1)
+        assert (onh["gn_ws"].cpu().reshape(1, 16, 32, 2) - part).abs().max().item() <= 1e-3 * part.abs().max().item() + 1e-3
+    else:
+        REF.igemm(x, w, o_ref, **rkw, **host)
+    close(o, o_ref, *tol, family)

@@ -14,8 +14,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
-EPI_GNAPPLY_SILU = 65536
+from progressive_stable_diffusion_amd.lib import (EPI_BIAS, EPI_GELU, EPI_GEGLU, EPI_GNAPPLY_SILU, EPI_LNFOLD, EPI_QUICKGELU,
+                                                 EPI_RESIDUAL, EPI_ROWVEC, EPI_SIGMOID, PRE_GN_SILU)
 
 
 def geglu_deinterleave_index(n: int) -> torch.Tensor:
@@ -148,11 +148,11 @@ class TorchRefBackend:
                 wsc = self.c(cat).reshape(bsz, 1, 32, 2).contiguous().reshape(-1)
                 xc = torch.cat([x, x2], dim=-1)
                 xn = torch.empty_like(xc)
-                self.groupnorm(xc, None, gam, bet, xn, wsc, 32, eps_in, 1 if flags & 16384 else 0, ws_chunks=1)
+                self.groupnorm(xc, None, gam, bet, xn, wsc, 32, eps_in, 1 if flags & PRE_GN_SILU else 0, ws_chunks=1)
                 x, x2 = xn[..., :c1_].contiguous(), xn[..., c1_:].contiguous()
             else:
                 xn = torch.empty_like(x)
-                self.groupnorm(x, None, gam, bet, xn, ws_in, 32, eps_in, 1 if flags & 16384 else 0, ws_chunks=nch_in)
+                self.groupnorm(x, None, gam, bet, xn, ws_in, 32, eps_in, 1 if flags & PRE_GN_SILU else 0, ws_chunks=nch_in)
                 x = xn
         xin = self.c(x) if x2 is None else torch.cat([self.c(x), self.c(x2)], dim=-1)
         b, hi, wi, cin = xin.shape
@@ -172,7 +172,7 @@ class TorchRefBackend:
             y = self.conv2d(xn, wt, None, stride=stride, padding=pad)
         assert y.shape[2] == ho and y.shape[3] == wo, (y.shape, out.shape)
         y = y.permute(0, 2, 3, 1)
-        if flags & 128:                 # EPI_LNFOLD: rstd * (x (gamma o W)^T - mu * c1), statistics of the fp16 rows
+        if flags & EPI_LNFOLD:          # rstd * (x (gamma o W)^T - mu * c1), statistics of the fp16 rows
             if ln_stats_in is not None:     # row partials [P][M][2] written by the producer of x (EPI_LNSTAT)
                 st = self.c(ln_stats_in).sum(dim=0).reshape(b, hi, wi, 2) / cin
                 mu, var = st[..., 0:1], st[..., 1:2] - st[..., 0:1] ** 2
@@ -180,18 +180,18 @@ class TorchRefBackend:
                 mu = xin.mean(dim=-1, keepdim=True)
                 var = (xin * xin).mean(dim=-1, keepdim=True) - mu * mu
             y = torch.rsqrt(var.clamp_min(0.0) + ln_eps) * (y - mu * self.c(ln_c1))
-        act = flags & (256 | 512 | 1024)
+        act = flags & (EPI_QUICKGELU | EPI_GELU | EPI_SIGMOID)
         gn_apply_silu = bool(flags & EPI_GNAPPLY_SILU)
-        flags &= 15                     # tuning bits (16, 32) do not change the math
+        flags &= EPI_BIAS | EPI_ROWVEC | EPI_RESIDUAL | EPI_GEGLU      # the tuning bits do not change the math
         if flags & EPI_BIAS:
             y = y + self.c(bias)
         if flags & EPI_ROWVEC:
             y = y + self.c(rowvec)[:, None, None, :]
-        if act & 256:
+        if act & EPI_QUICKGELU:
             y = y * torch.sigmoid(1.702 * y)
-        elif act & 512:
+        elif act & EPI_GELU:
             y = F.gelu(y)
-        elif act & 1024:
+        elif act & EPI_SIGMOID:
             y = torch.sigmoid(y)
         if flags & EPI_GEGLU:
             y = y[..., geglu_deinterleave_index(n).argsort().to(y.device)]   # undo the physical row order
