@@ -107,6 +107,7 @@ class HipBackend:
         self.stream = torch.cuda.Stream(device=self.device)
         self._desc = L.IgemmDesc()
         self._wdesc = L.WgradDesc()
+        self._gdesc = L.GnGradDesc()
         self._n_cu = None
         self._capturing = False     # between graph_begin() and graph_end(): no cross-stream waits may be recorded
         self._prof_on = False
@@ -346,6 +347,99 @@ class HipBackend:
         m = x.numel() // c
         fn = getattr(self.lib, "dadd_layernorm_" + _sfx(x, out))
         L.check(fn(_p(x), _p(gamma), _p(beta), _p(out), m, c, float(eps), self.s))
+
+    # -- training backward of the norms and GEGLU (csrc/norm_grad.hip)
+    def groupnorm_grad_ws_numel(self, b, hw, c, groups):
+        """fp32 elements of the ``ws`` scratch of a ``groupnorm_grad`` call: the chunk partials of the statistics, of
+        s1 / s2 and of the channel sums (include/dadd_hip_norm_grad.h)."""
+        n = int(self.lib.dadd_groupnorm_grad_ws_floats(b, hw, c, groups))
+        if n < 0:
+            raise ValueError(f"groupnorm_grad takes C a multiple of 8 up to 4096 and groups <= 32 dividing C "
+                             f"(got B {b}, HW {hw}, C {c}, groups {groups})")
+        return n
+
+    def groupnorm_grad(self, x1, x2, dy, gamma, beta, *, dx1=None, dx2=None, dgamma=None, dbeta=None, ws, groups, eps,
+                       silu):
+        """Backward of ``groupnorm``: from the forward's input x1 [B,H,W,C1] (+ x2 [B,H,W,C2], a skip-concat) and
+        dy [B,H,W,C1+C2], all fp16 or all bf16, dx1 / dx2 in the same type and dgamma / dbeta [C] in fp32, overwritten.
+        Mean and rstd are recomputed from x; with ``silu`` dy is first taken through the derivative of SiLU at the
+        normalised value.  ``dx1`` None: parameter gradients only; ``dgamma`` and ``dbeta`` None: data gradient only.
+        ``ws`` is fp32 scratch of ``groupnorm_grad_ws_numel`` elements.  Four launches (statistics, chunk partials,
+        apply, column sums), every sum in a fixed order: the result is bit-reproducible."""
+        if x1.dim() != 4 or dy.dim() != 4:
+            raise ValueError(f"groupnorm_grad takes NHWC tensors, got {tuple(x1.shape)} and {tuple(dy.shape)}")
+        b, hw, c1 = x1.shape[0], x1.shape[1] * x1.shape[2], x1.shape[-1]
+        c2 = 0 if x2 is None else x2.shape[-1]
+        c = c1 + c2
+        fn = getattr(self.lib, "dadd_groupnorm_grad_" + _sfx(x1, x2, dy, dx1, dx2))
+        need = self.groupnorm_grad_ws_numel(b, hw, c, groups)
+        if c1 % 8 or c2 % 8:
+            raise ValueError(f"groupnorm_grad: C1 = {c1} and C2 = {c2} must be multiples of 8")
+        for t in (x1, x2, dy, dx1, dx2):
+            assert t is None or (t.is_contiguous() and t.dtype in _SFX), "16-bit contiguous tensors expected"
+        assert dy.shape == x1.shape[:-1] + (c,) and (x2 is None or x2.shape[:-1] == x1.shape[:-1])
+        assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == c \
+            and gamma.is_contiguous() and beta.is_contiguous()
+        assert (dgamma is None) == (dbeta is None) and (dx1 is not None or dgamma is not None)
+        assert dgamma is None or (dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c
+                                  and dgamma.is_contiguous() and dbeta.is_contiguous())
+        assert (dx1 is None or dx1.shape == x1.shape) and ((dx2 is not None) == (dx1 is not None and x2 is not None)) \
+            and (dx2 is None or dx2.shape == x2.shape)
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, (ws.shape, need)
+        d = self._gdesc
+        d.x1, d.x2, d.dy, d.gamma, d.beta = _p(x1), _p(x2), _p(dy), _p(gamma), _p(beta)
+        d.dx1, d.dx2, d.dgamma, d.dbeta, d.ws = _p(dx1), _p(dx2), _p(dgamma), _p(dbeta), _p(ws)
+        d.B, d.HW, d.C1, d.C2, d.groups, d.silu, d.eps = b, hw, c1, c2, int(groups), int(bool(silu)), float(eps)
+        L.check(fn(C.byref(d), self.s))
+
+    def layernorm_grad_ws_numel(self, m, c):
+        """fp32 elements of the ``ws`` scratch of ``layernorm_grad``: per-workgroup column sums [nblk][C][2]."""
+        n = int(self.lib.dadd_layernorm_grad_ws_floats(m, c))
+        if n < 0:
+            raise ValueError(f"layernorm_grad takes C a multiple of 8 up to 2048 and at least one row (got M {m}, C {c})")
+        return n
+
+    def layernorm_grad(self, x, dy, gamma, *, dx=None, dgamma=None, dbeta=None, ws=None, eps=1e-5):
+        """Backward of ``layernorm`` over the last axis: from the forward's input x [..., C] and dy of the same shape (fp16
+        or bf16), dx in the same type and dgamma / dbeta [C] in fp32, overwritten.  Mean and rstd of every row are
+        recomputed (two-pass).  ``dx`` None: parameter gradients only; ``dgamma`` and ``dbeta`` None: data gradient only.
+        The parameter gradients need ``ws``, fp32 scratch of ``layernorm_grad_ws_numel`` elements.  One launch over the
+        rows and one for the column sums, fixed summation order: bit-reproducible."""
+        c = x.shape[-1]
+        m = x.numel() // max(c, 1)
+        fn = getattr(self.lib, "dadd_layernorm_grad_" + _sfx(x, dy, dx))
+        need = self.layernorm_grad_ws_numel(m, c)
+        for t in (x, dy, dx):
+            assert t is None or (t.is_contiguous() and t.dtype in _SFX and t.shape == x.shape), "x, dy, dx: one 16-bit shape"
+        assert gamma.dtype == torch.float32 and gamma.numel() == c and gamma.is_contiguous()
+        assert (dgamma is None) == (dbeta is None) and (dx is not None or dgamma is not None)
+        if dgamma is not None:
+            assert dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c \
+                and dgamma.is_contiguous() and dbeta.is_contiguous()
+            assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        L.check(fn(_p(x), _p(dy), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), _p(ws), m, c, float(eps), self.s))
+
+    def geglu(self, h, y):
+        """GEGLU as a layer of its own: h [..., 2F] with the hidden half in [..., :F] and the gate in [..., F:] (chunk(2)
+        order, not the interleaved weight rows of EPI_GEGLU) -> y [..., F] = hidden * gelu(gate), fp16 or bf16.  The
+        training step keeps h for ``geglu_grad``; the inference plans keep the GEMM epilogue."""
+        f = y.shape[-1]
+        fn = getattr(self.lib, "dadd_geglu_" + _sfx(h, y))
+        if f % 8 or f == 0:
+            raise ValueError(f"geglu: F = {f} must be a positive multiple of 8")
+        assert h.shape == y.shape[:-1] + (2 * f,) and h.is_contiguous() and y.is_contiguous() and h.dtype in _SFX
+        L.check(fn(_p(h), _p(y), h.numel() // (2 * f), f, self.s))
+
+    def geglu_grad(self, h, dy, dh):
+        """Backward of ``geglu``: dh[..., :F] = dy * gelu(gate) and dh[..., F:] = dy * hidden * gelu'(gate), gelu' from the
+        same erf approximation as the forward.  h and dh [..., 2F], dy [..., F], all fp16 or all bf16."""
+        f = dy.shape[-1]
+        fn = getattr(self.lib, "dadd_geglu_grad_" + _sfx(h, dy, dh))
+        if f % 8 or f == 0:
+            raise ValueError(f"geglu_grad: F = {f} must be a positive multiple of 8")
+        assert h.shape == dy.shape[:-1] + (2 * f,) and dh.shape == h.shape and h.dtype in _SFX
+        assert h.is_contiguous() and dy.is_contiguous() and dh.is_contiguous()
+        L.check(fn(_p(h), _p(dy), _p(dh), h.numel() // (2 * f), f, self.s))
 
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""

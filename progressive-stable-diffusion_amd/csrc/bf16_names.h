@@ -26,6 +26,13 @@
 #define conv_cout4_kernel conv_cout4_kernel_bf16
 #define wgrad_kernel wgrad_kernel_bf16
 #define wgrad_finish_kernel wgrad_finish_kernel_bf16
+#define gn_grad_stats_kernel gn_grad_stats_kernel_bf16
+#define gn_grad_partial_kernel gn_grad_partial_kernel_bf16
+#define gn_grad_apply_kernel gn_grad_apply_kernel_bf16
+#define norm_grad_finish_kernel norm_grad_finish_kernel_bf16
+#define layernorm_grad_kernel layernorm_grad_kernel_bf16
+#define geglu_kernel geglu_kernel_bf16
+#define geglu_grad_kernel geglu_grad_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -52,3 +59,9 @@
 #define dadd_conv3x3_cout4_f16 dadd_conv3x3_cout4_bf16
 #define dadd_conv_out_ddim_f16 dadd_conv_out_ddim_bf16
 #define dadd_conv_wgrad_f16 dadd_conv_wgrad_bf16
+
+// C entry points (include/dadd_hip_norm_grad.h)
+#define dadd_groupnorm_grad_f16 dadd_groupnorm_grad_bf16
+#define dadd_layernorm_grad_f16 dadd_layernorm_grad_bf16
+#define dadd_geglu_f16 dadd_geglu_bf16
+#define dadd_geglu_grad_f16 dadd_geglu_grad_bf16

@@ -18,7 +18,9 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            "igemm_bf16.hip", "igemm_dma_bf16.hip", "conv_halo_bf16.hip", "norm_bf16.hip", "attention_bf16.hip",
            "elementwise_bf16.hip",
            # training backward: the M-reduction GEMM of the weight gradient and its bf16 twin
-           "wgrad.hip", "wgrad_bf16.hip")
+           "wgrad.hip", "wgrad_bf16.hip",
+           # training backward: GroupNorm(+SiLU) / LayerNorm / GEGLU and the plain GEGLU forward, and their bf16 twin
+           "norm_grad.hip", "norm_grad_bf16.hip")
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -56,6 +58,12 @@ class WgradDesc(C.Structure):
     _fields_ = [(n, vp) for n in ("dy", "x", "dw", "dbias", "partial")] + \
                [(n, i32) for n in ("B", "Hi", "Wi", "C", "Ho", "Wo", "N", "taps", "stride", "ups", "pad",
                                    "ld_dy", "ld_x", "ld_dw", "ld_tap", "splitm")]
+
+
+class GnGradDesc(C.Structure):
+    """Mirror of ``dadd_gn_grad_desc``."""
+    _fields_ = [(n, vp) for n in ("x1", "x2", "dy", "gamma", "beta", "dx1", "dx2", "dgamma", "dbeta", "ws")] + \
+               [(n, i32) for n in ("B", "HW", "C1", "C2", "groups", "silu")] + [("eps", f32)]
 
 
 # name -> (restype, argtypes); every symbol include/dadd_hip.h declares
@@ -134,6 +142,21 @@ GRAD_PROTOTYPES = {
     "dadd_conv_wgrad_bf16": (C.c_int, [C.POINTER(WgradDesc), vp]),
 }
 
+# every symbol include/dadd_hip_norm_grad.h declares (training backward of the norms and GEGLU, csrc/norm_grad.hip)
+_LN_GRAD = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp])
+NORM_GRAD_PROTOTYPES = {
+    "dadd_groupnorm_grad_f16": (C.c_int, [C.POINTER(GnGradDesc), vp]),
+    "dadd_groupnorm_grad_bf16": (C.c_int, [C.POINTER(GnGradDesc), vp]),
+    "dadd_groupnorm_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dadd_layernorm_grad_f16": _LN_GRAD,
+    "dadd_layernorm_grad_bf16": _LN_GRAD,
+    "dadd_layernorm_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int]),
+    "dadd_geglu_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_geglu_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_geglu_grad_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_geglu_grad_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -142,7 +165,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
-        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h")]
+        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -168,7 +191,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension is required (run __graft_entry__.build()); "
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
