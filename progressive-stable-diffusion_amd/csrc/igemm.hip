@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int tile_id = xcd_remap(blockIdx.x, gridDim.x);
   int nt, mt;
-  tile_decode(p, tile_id, mt, nt);
+  tile_decode_fast(p, tile_id, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int z = blockIdx.y;
   const int kt0 = z * p.kps;
@@ -64,10 +64,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs p) {
     const int m = m0 + r0 + 32 * i;
     const bool ok = m < p.M;
     const int mm = ok ? m : 0;
-    const int b = mm / HoWo;
-    const int rem = mm - b * HoWo;
-    const int oy = rem / p.Wo;
-    const int ox = rem - oy * p.Wo;
+    int b, oy, ox;
+    row_decode(p, mm, HoWo, b, oy, ox);
     a_pix[i] = b * p.Hi * p.Wi;
     a_y[i] = ok ? oy * p.stride - p.pad : -100000;  // invalid rows fail every bounds test
     a_x[i] = ox * p.stride - p.pad;
@@ -599,6 +597,31 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
                           a.mtiles * a.ntiles > num_cu;
   if (persistent && ((d->flags & DADD_TUNE_SHALLOW) ? false : 2.0 * a.B * a.Hi * a.Wi * Cin >= 2.0 * a.N * a.K))
     a.gm = a.gn = 0;
+  // division-free prologue (igemm_args.h, fastdiv.h): multipliers of every run-time divisor of the kernels
+  a.fd_on = (size_t)a.B * a.Ho * a.Wo < DADD_FASTDIV_MAX && (size_t)a.K < DADD_FASTDIV_MAX &&
+            (size_t)a.mtiles * a.ntiles < DADD_FASTDIV_MAX;
+  a.plain = a.taps == 1 && a.stride == 1 && a.pad == 0 && !a.ups && a.Ho == a.Hi && a.Wo == a.Wi;
+  if (a.fd_on) {
+    a.fd_howo = dadd_fastdiv_make((uint32_t)(a.Ho * a.Wo));
+    a.fd_wo = dadd_fastdiv_make((uint32_t)a.Wo);
+    a.fd_cin = dadd_fastdiv_make((uint32_t)Cin);
+    a.ngn = 1;
+    a.fd_t1 = a.fd_t2 = dadd_fastdiv_make(1);
+    if (a.gm == 0) {
+      a.fd_t0 = dadd_fastdiv_make((uint32_t)a.ntiles);
+    } else if (a.gn >= a.ntiles) {
+      a.fd_t0 = dadd_fastdiv_make((uint32_t)(a.gm * a.ntiles));
+      a.fd_t1 = dadd_fastdiv_make((uint32_t)a.gm);
+    } else if (a.gm >= a.mtiles) {
+      a.fd_t0 = dadd_fastdiv_make((uint32_t)(a.mtiles * a.gn));
+      a.fd_t1 = dadd_fastdiv_make((uint32_t)a.mtiles);
+    } else {
+      a.ngn = a.ntiles / a.gn;
+      a.fd_t0 = dadd_fastdiv_make((uint32_t)(a.gm * a.gn));
+      a.fd_t1 = dadd_fastdiv_make((uint32_t)a.gm);
+      a.fd_t2 = dadd_fastdiv_make((uint32_t)a.ngn);
+    }
+  }
   // 3x3 / stride 1 on whole-row tiles: the halo-resident kernel (conv_halo.hip); K slices = channel chunks
   const bool halo = dma && tile_m == 128 && dadd_conv_halo_applicable(a, tile_n);
   int halo_ns = 1;

@@ -1,6 +1,7 @@
 // Kernel argument block shared by the two implicit-GEMM kernels (igemm.hip, igemm_dma.hip).
 #pragma once
 #include "dadd_common.h"
+#include "fastdiv.h"
 
 struct IgemmArgs {
   const half_t* x;
@@ -37,7 +38,25 @@ struct IgemmArgs {
   int M, K, nkt, kps, ntiles;
   int korder;           // LDS-DMA kernel only: 0 = channels fastest, 1 = taps fastest (3x3)
   int mtiles, gm, gn;   // tile order: groups of gm x gn tiles (one of them spans its whole dimension); gm == 0: n fastest
+  // Division-free prologue (fastdiv.h), filled by dadd_igemm_resolve.  fd_on: M, K and the tile count are below 2^24, so
+  // every dividend of the kernels is in range; otherwise the kernels divide.  plain: a linear layer (one tap, stride 1,
+  // no padding, output map == input map) — output row m reads input pixel m, no decode at all.
+  int fd_on, plain;
+  dadd_fastdiv fd_howo, fd_wo, fd_cin;   // row -> (sample, y, x); K offset -> tap
+  dadd_fastdiv fd_t0, fd_t1, fd_t2;      // tile_decode: tiles per group (or ntiles), row tiles per group, column groups
+  int ngn;                               // ntiles / gn (2-D groups)
 };
+
+// output row -> sample (rowvec / GroupNorm-statistics addressing) and -> (sample, y, x) (the im2col gather)
+__device__ __forceinline__ int row_sample(const IgemmArgs& p, int m, int HoWo) {
+  return p.fd_on ? (int)dadd_fastdiv_div((uint32_t)m, p.fd_howo) : m / HoWo;
+}
+__device__ __forceinline__ void row_decode(const IgemmArgs& p, int m, int HoWo, int& b, int& oy, int& ox) {
+  b = row_sample(p, m, HoWo);
+  const int rem = m - b * HoWo;
+  oy = p.fd_on ? (int)dadd_fastdiv_div((uint32_t)rem, p.fd_wo) : rem / p.Wo;
+  ox = rem - oy * p.Wo;
+}
 
 // XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (id % 8 shares an XCD, each
 // with a private 4 MiB L2).  Remap so that one XCD owns a CONTIGUOUS range of logical tiles: row
@@ -81,6 +100,38 @@ __device__ __forceinline__ void tile_decode(const IgemmArgs& p, int tile_id, int
     const int gmi = g / ngn, gni = g - gmi * ngn;
     mt = gmi * p.gm + idx % p.gm;
     nt = gni * p.gn + idx / p.gm;
+  }
+}
+
+// The same map with the quotients taken by multiply and shift (fd_t0 / fd_t1 / fd_t2, filled by dadd_igemm_resolve): for
+// a wave-uniform id that is s_mul_hi_u32 + s_lshr_b32 on the scalar unit instead of a VALU division sequence per
+// quotient.  Used by igemm_dma.hip and igemm.hip.  The halo conv keeps tile_decode: two wave-uniform quotients per launch
+// and no per-lane decode — nothing was gained there (profiles/r07_b_step_profile_abc.txt).
+__device__ __forceinline__ void tile_decode_fast(const IgemmArgs& p, int tile_id, int& mt, int& nt) {
+  const auto div = [&](int n, const dadd_fastdiv& f, int d) { return p.fd_on ? (int)dadd_fastdiv_div((uint32_t)n, f) : n / d; };
+  if (p.gm == 0) {
+    mt = div(tile_id, p.fd_t0, p.ntiles);
+    nt = tile_id - mt * p.ntiles;
+  } else if (p.gn >= p.ntiles) {          // groups of gm row tiles x all column tiles
+    const int per = p.gm * p.ntiles;
+    const int g = div(tile_id, p.fd_t0, per), idx = tile_id - g * per;
+    const int base = g * p.gm;
+    const int gsz = min(p.gm, p.mtiles - base);
+    nt = gsz == p.gm ? div(idx, p.fd_t1, p.gm) : idx / gsz;      // (the last group may be short)
+    mt = base + idx - nt * gsz;
+  } else if (p.gm >= p.mtiles) {          // groups of all row tiles x gn column tiles
+    const int per = p.mtiles * p.gn;
+    const int g = div(tile_id, p.fd_t0, per), idx = tile_id - g * per;
+    const int q = div(idx, p.fd_t1, p.mtiles);
+    mt = idx - q * p.mtiles;
+    nt = g * p.gn + q;
+  } else {                                // 2-D groups of gm x gn tiles (the host guarantees gm | mtiles and gn | ntiles): an XCD
+    const int per = p.gm * p.gn;          // owns a block of A rows that STAYS in its L2 while the block's weight tiles stream by
+    const int g = div(tile_id, p.fd_t0, per), idx = tile_id - g * per;
+    const int gmi = div(g, p.fd_t2, p.ngn), gni = g - gmi * p.ngn;
+    const int q = div(idx, p.fd_t1, p.gm);
+    mt = gmi * p.gm + idx - q * p.gm;
+    nt = gni * p.gn + q;
   }
 }
 

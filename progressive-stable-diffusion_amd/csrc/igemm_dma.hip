@@ -110,9 +110,11 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
   unsigned a_v1[NA], a_v2[NA], a_mask[NA];
   int a_pix[NA], a_y[NA], a_x[NA], a_cc[NA];   // only the upsample path uses these per tile
   unsigned w_v[NBJ];
-  auto setup_tile = [&](int tile_id) {
+  // (always_inline: with PERS the call sites inside issue() made the compiler emit this lambda as a function of its own,
+  // which put the whole argument block and the gather state in scratch)
+  auto setup_tile = [&](int tile_id) __attribute__((always_inline)) {
   int nt, mt;
-  tile_decode(p, tile_id, mt, nt);
+  tile_decode_fast(p, tile_id, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
@@ -120,25 +122,31 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
     const int m = m0 + row;
     const bool ok = m < p.M;
     const int mm = ok ? m : 0;
-    const int b = mm / HoWo;
-    const int rem = mm - b * HoWo;
-    const int oy = rem / p.Wo;
-    const int ox = rem - oy * p.Wo;
     const int cc = (lch ^ ((row >> 1) & 7)) * 8;   // logical chunk this lane fetches (halfs)
+    if (!UPS && p.plain) {    // launch-uniform.  A linear layer: output row m reads input pixel m — nothing to decode
+      a_v1[i] = (unsigned)((mm * p.C1 + cc) * 2);
+      a_v2[i] = (unsigned)((mm * p.C2 + cc) * 2);
+      a_mask[i] = ok ? 1u : 0u;
+      continue;
+    }
+    int b, oy, ox;
+    row_decode(p, mm, HoWo, b, oy, ox);
     const int pix = b * p.Hi * p.Wi;
     const int y0 = oy * p.stride - p.pad, x0 = ox * p.stride - p.pad;
     a_pix[i] = pix; a_y[i] = ok ? y0 : -100000; a_x[i] = x0; a_cc[i] = cc;
     const int org = pix + oy * p.stride * p.Wi + ox * p.stride;
     a_v1[i] = (unsigned)((org * p.C1 + cc) * 2);
     a_v2[i] = (unsigned)((org * p.C2 + cc) * 2);
-    unsigned mask = 0;
-    const int ntap = p.taps;
-    for (int tp = 0; tp < ntap; ++tp) {
-      const int ky = (ntap == 9) ? tp / 3 : 0, kx = (ntap == 9) ? tp - 3 * ky : 0;
-      const int iy = y0 + ky, ix = x0 + kx;
-      if (ok && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv) mask |= 1u << tp;
+    // bit tp = 3 ky + kx of the mask: tap (ky, kx) of this row's window lies inside the image — the three row bits and
+    // the three column bits combined, instead of nine bounds tests in a loop
+    unsigned my = 0, mx = 0;
+#pragma unroll
+    for (int k3 = 0; k3 < 3; ++k3) {
+      my |= (y0 + k3 >= 0 && y0 + k3 < Hv) ? 1u << k3 : 0u;
+      mx |= (x0 + k3 >= 0 && x0 + k3 < Wv) ? 1u << k3 : 0u;
     }
-    a_mask[i] = mask;
+    const unsigned mask9 = ((my & 1u) ? mx : 0u) | ((my & 2u) ? mx << 3 : 0u) | ((my & 4u) ? mx << 6 : 0u);
+    a_mask[i] = ok ? (p.taps == 9 ? mask9 : (my & mx & 1u)) : 0u;
   }
 #pragma unroll
   for (int j = 0; j < NBJ; ++j) {
@@ -147,7 +155,6 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
     w_v[j] = (n < p.N) ? (unsigned)(((size_t)n * p.K + (lch ^ ((row >> 1) & 7)) * 8) * 2) : OOB;
   }
   };
-  setup_tile(tile_first);
   int iss_tile = tile_first, iss_left = tile_count;   // PERS: the tile the DMA cursor is in / tiles left
 
   // ---- wave-uniform tile cursor, advanced incrementally (no divisions in the loop): K tile -> tap,
@@ -158,14 +165,21 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
   // chunk) and can hit in the CU's L1 instead of each going to L2.  Same products, different
   // summation order.
   const bool tapfast = p.korder != 0;
+  // The cursor and the per-lane gather state belong to the LOADER waves: both are set up behind the role split below
+  // (cursor_init, setup_tile), so the MFMA waves, which share their SIMD's VALU with a loader wave, run none of it.
   int cur_kt = kt0;
-  // (the runtime division runs on the VALU: pin the wave-uniform results to SGPRs, or the scalar offset
-  // operand of every weight DMA is legalised with a waterfall loop)
-  int cur_tap = __builtin_amdgcn_readfirstlane(tapfast ? kt0 % 9 : (kt0 * BK) / Cin);
-  int cur_c = __builtin_amdgcn_readfirstlane(tapfast ? (kt0 / 9) * BK : kt0 * BK - cur_tap * Cin);
-  int cur_koff = __builtin_amdgcn_readfirstlane((cur_tap * Cin + cur_c) * 2);   // byte offset of the K tile in a weight row
-  int cur_ky = (p.taps == 9) ? cur_tap / 3 : 0;
-  int cur_kx = (p.taps == 9) ? cur_tap - 3 * cur_ky : 0;
+  int cur_tap = 0, cur_c = 0, cur_koff = 0, cur_ky = 0, cur_kx = 0;
+  auto cursor_init = [&]() {
+    if (kt0 == 0) return;      // wave-uniform: every launch without split-K, and the first K slice
+    // (pin the wave-uniform results to SGPRs, or the scalar offset operand of every weight DMA is legalised with a
+    // waterfall loop)
+    const int tap0 = p.fd_on ? (int)dadd_fastdiv_div((uint32_t)(kt0 * BK), p.fd_cin) : (kt0 * BK) / Cin;
+    cur_tap = __builtin_amdgcn_readfirstlane(tapfast ? kt0 % 9 : tap0);
+    cur_c = __builtin_amdgcn_readfirstlane(tapfast ? (kt0 / 9) * BK : kt0 * BK - cur_tap * Cin);
+    cur_koff = __builtin_amdgcn_readfirstlane((cur_tap * Cin + cur_c) * 2);   // byte offset of the K tile in a weight row
+    cur_ky = (p.taps == 9) ? cur_tap / 3 : 0;
+    cur_kx = (p.taps == 9) ? cur_tap - 3 * cur_ky : 0;
+  };
   int fill_off = wave * 1024;                 // LDS byte offset of this wave's share of the slot to fill
 
   // One K tile of DMA work, split so that the pieces can be interleaved with MFMAs:
@@ -271,6 +285,8 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
   const bool ln_sts = ln_stage && ln_lds_stats(p, LN_LDS_BYTES);
   if (loader) {
     const int ln_extra = ln_stage ? ln_lds_count(p, wave, ln_sts) : 0;      // extras this wave issues per output tile
+    cursor_init();
+    setup_tile(tile_first);
     issue();
     issue();
     issue();
@@ -298,7 +314,7 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
       if (ln_stage) {
         if (kc == 0) {
           int nt, mt;
-          tile_decode(p, ext_tile, mt, nt);
+          tile_decode_fast(p, ext_tile, mt, nt);
           ln_lds_issue<BN>(p, ln_scr, __builtin_amdgcn_readfirstlane(mt) * BM, __builtin_amdgcn_readfirstlane(nt) * BN, wave,
                            lane, ln_sts);
           ext_young = ln_extra > 0;
@@ -385,7 +401,7 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
       __builtin_amdgcn_sched_barrier(0);
     }
     int nt, mt;
-    tile_decode(p, tile_first + tl, mt, nt);
+    tile_decode_fast(p, tile_first + tl, mt, nt);
     if constexpr (LNF) {
       ln_finish<MI>(ls1, ls2, p.K, p.ln_eps);
       igemm_epilogue<J, MI, WM, WN>(p, acc, mt * BM, nt * BN, wm, wn, lane, z, smem, ls1, ls2);

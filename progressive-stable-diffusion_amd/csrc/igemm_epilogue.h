@@ -85,7 +85,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
     // Sums are taken over the ROUNDED fp16 values (what the consumer reads), in a fixed order: bit-reproducible.
     float* scratch = reinterpret_cast<float*>(gn_scratch) + (wm * 2 + wn) * 256;   // [WN <= 80][2] per wave
     const int mrow0 = m0 + wm * WM;
-    const int bsmp = mrow0 / HoWo;
+    const int bsmp = row_sample(p, mrow0, HoWo);
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       const int n = n0 + wn * WN + j * 16 + g * 4;
@@ -240,7 +240,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
         if (n >= p.N) continue;
         f4 v = lrs[i] * (acc[j][i] - lmu[i] * *reinterpret_cast<const f4*>(ln_cb + c * 4));
         if (p.flags & DADD_EPI_BIAS) v += *reinterpret_cast<const f4*>(ln_cb + 1024 + c * 4);
-        if (p.flags & DADD_EPI_ROWVEC) v += *reinterpret_cast<const f4*>(p.rowvec + (size_t)(m / HoWo) * p.ld_rowvec + n);
+        if (p.flags & DADD_EPI_ROWVEC) v += *reinterpret_cast<const f4*>(p.rowvec + (size_t)row_sample(p, m, HoWo) * p.ld_rowvec + n);
         if (p.flags & DADD_EPI_ACT_MASK) {
           if (p.flags & DADD_EPI_QUICKGELU) {
 #pragma unroll
@@ -310,7 +310,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
         const int m = m0 + wm * WM + i * 16 + mc;
         if (m >= p.M) continue;
         f4 v = lrs[i] * (acc[j][i] - lmu[i] * c4) + b4;
-        if (p.flags & DADD_EPI_ROWVEC) v += *reinterpret_cast<const f4*>(p.rowvec + (size_t)(m / HoWo) * p.ld_rowvec + n);
+        if (p.flags & DADD_EPI_ROWVEC) v += *reinterpret_cast<const f4*>(p.rowvec + (size_t)row_sample(p, m, HoWo) * p.ld_rowvec + n);
         if (p.flags & DADD_EPI_ACT_MASK) {
           if (p.flags & DADD_EPI_QUICKGELU) {
 #pragma unroll
@@ -339,7 +339,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
   for (int i = 0; i < MI; ++i) {
     const int m = m0 + wm * WM + i * 16 + mc;
     if (m >= p.M) continue;
-    const int b = m / HoWo;
+    const int b = (p.flags & DADD_EPI_ROWVEC) ? row_sample(p, m, HoWo) : 0;   // (only the time-embedding row needs the sample)
     float rs1 = 0.f, rs2 = 0.f;      // DADD_EPI_LNSTAT: this lane's share of row m (J x 4 columns)
     if (p.flags & DADD_EPI_GEGLU) {
       if constexpr (J == 4) {
