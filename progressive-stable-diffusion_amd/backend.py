@@ -108,6 +108,7 @@ class HipBackend:
         self._desc = L.IgemmDesc()
         self._wdesc = L.WgradDesc()
         self._gdesc = L.GnGradDesc()
+        self._adesc = L.AttnGradDesc()
         self._n_cu = None
         self._capturing = False     # between graph_begin() and graph_end(): no cross-stream waits may be recorded
         self._prof_on = False
@@ -440,6 +441,63 @@ class HipBackend:
         assert h.shape == dy.shape[:-1] + (2 * f,) and dh.shape == h.shape and h.dtype in _SFX
         assert h.is_contiguous() and dy.is_contiguous() and dh.is_contiguous()
         L.check(fn(_p(h), _p(dy), _p(dh), h.numel() // (2 * f), f, self.s))
+
+    # -- training backward of attention (csrc/attn_grad.hip)
+    def attn_grad_ws_numel(self, b, heads, nq):
+        """fp32 elements of the ``ws`` scratch of an ``attn_grad`` call: (LSE, D) per (sample, head, query row)."""
+        n = int(self.lib.dadd_attn_grad_ws_floats(b, heads, nq))
+        if n < 0:
+            raise ValueError(f"attn_grad takes positive sizes (got B {b}, heads {heads}, Nq {nq})")
+        return n
+
+    @staticmethod
+    def _token_ld(t, what):
+        """(row stride, sample stride) of a [B,N,C] view: a column block of wider rows and / or a token range of a
+        longer sequence."""
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise ValueError(f"attn_grad: {what} must be a [B,N,C] view with unit column stride, got shape "
+                             f"{tuple(t.shape)} strides {t.stride()}")
+        return t.stride(1), (t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.stride(1))
+
+    def attn_grad(self, q, k, v, dout, *, dq=None, dk=None, dv=None, ws, heads, do_scale=1.0, do_scale_dev=None):
+        """Backward of ``attention`` / ``self_attn``: from q, dout [B,Nq,C] and k, v [B,Nk,C] (fp16 or bf16, strided 3-D
+        views: column blocks of wider rows are fine, k and v share one row stride) the gradients dq [B,Nq,C] and
+        dk, dv [B,Nk,C] (one row stride) of softmax(q k^T / sqrt(d)) v, for dout * do_scale * do_scale_dev[0]
+        (``do_scale_dev``: device fp32[1], read by the kernels).  Each output may be None; without dk and dv the dkv launch
+        is skipped, without dq the dq launch.  ``ws`` is fp32 scratch of ``attn_grad_ws_numel`` elements.  Up to three
+        launches (row statistics, dK / dV, dQ), fixed summation order: bit-reproducible.  d in {40, 80, 160}; Nq and Nk
+        multiples of 16."""
+        fn = getattr(self.lib, "dadd_attn_grad_" + _sfx(q, k, v, dout, dq, dk, dv))
+        for t in (q, k, v, dout, dq, dk, dv):
+            if t is not None and t.dtype not in _SFX:
+                raise ValueError(f"attn_grad takes 16-bit tensors, got {t.dtype}")
+        b, nq, c = q.shape
+        nk = k.shape[1]
+        if c % heads:
+            raise ValueError(f"attn_grad: C = {c} is not a multiple of heads = {heads}")
+        if dq is None and dk is None and dv is None:
+            raise ValueError("attn_grad: no output")
+        assert dout.shape == q.shape and k.shape == (b, nk, c) and v.shape == k.shape
+        assert all(t is None or t.shape == q.shape for t in (dq,)) and all(t is None or t.shape == k.shape for t in (dk, dv))
+        (ld_q, bs_q), (ld_kv, bs_kv), (ld_do, bs_do) = self._token_ld(q, "q"), self._token_ld(k, "k"), self._token_ld(dout, "dout")
+        if self._token_ld(v, "v") != (ld_kv, bs_kv):
+            raise ValueError("attn_grad: k and v must share their strides")
+        ld_dq, bs_dq = self._token_ld(dq, "dq") if dq is not None else (0, 0)
+        lds = {self._token_ld(t, "dk / dv") for t in (dk, dv) if t is not None}
+        if len(lds) > 1:
+            raise ValueError("attn_grad: dk and dv must share their strides")
+        ld_dkv, bs_dkv = lds.pop() if lds else (0, 0)
+        need = self.attn_grad_ws_numel(b, heads, nq)
+        assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        assert do_scale_dev is None or (do_scale_dev.dtype == torch.float32 and do_scale_dev.numel() >= 1)
+        d = self._adesc
+        d.q, d.k, d.v, d.dout = _p(q), _p(k), _p(v), _p(dout)
+        d.dq, d.dk, d.dv, d.ws, d.do_scale_dev = _p(dq), _p(dk), _p(dv), _p(ws), _p(do_scale_dev)
+        d.B, d.Nq, d.Nk, d.heads, d.d = b, nq, nk, heads, c // heads
+        d.ld_q, d.ld_kv, d.ld_do, d.ld_dq, d.ld_dkv = ld_q, ld_kv, ld_do, ld_dq, ld_dkv
+        d.bs_q, d.bs_kv, d.bs_do, d.bs_dq, d.bs_dkv = bs_q, bs_kv, bs_do, bs_dq, bs_dkv
+        d.do_scale = float(do_scale)
+        L.check(fn(C.byref(d), self.s))
 
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""

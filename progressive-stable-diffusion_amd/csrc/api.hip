@@ -13,9 +13,11 @@ int dadd_init_norm();
 int dadd_init_attn2_fused();
 int dadd_init_ffn_block();
 int dadd_init_tf_head();
+int dadd_init_attn_grad();        // training backward of attention (attn_grad.hip)
 int dadd_init_igemm_bf16();      // the bf16 twins (*_bf16.hip)
 int dadd_init_attention_bf16();
 int dadd_init_norm_bf16();
+int dadd_init_attn_grad_bf16();
 
 namespace {
 thread_local char g_err[512] = "";
@@ -68,6 +70,8 @@ int dadd_init(void) {
   if (rc == DADD_OK) rc = dadd_init_igemm_bf16();
   if (rc == DADD_OK) rc = dadd_init_attention_bf16();
   if (rc == DADD_OK) rc = dadd_init_norm_bf16();
+  if (rc == DADD_OK) rc = dadd_init_attn_grad();
+  if (rc == DADD_OK) rc = dadd_init_attn_grad_bf16();
   return rc != DADD_OK ? rc : dadd_init_tf_head();
 }
 

@@ -33,6 +33,9 @@
 #define layernorm_grad_kernel layernorm_grad_kernel_bf16
 #define geglu_kernel geglu_kernel_bf16
 #define geglu_grad_kernel geglu_grad_kernel_bf16
+#define attn_grad_stats_kernel attn_grad_stats_kernel_bf16
+#define attn_grad_dkv_kernel attn_grad_dkv_kernel_bf16
+#define attn_grad_dq_kernel attn_grad_dq_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -45,6 +48,7 @@
 #define dadd_conv_halo_row dadd_conv_halo_row_bf16
 #define dadd_init_norm dadd_init_norm_bf16
 #define dadd_init_attention dadd_init_attention_bf16
+#define dadd_init_attn_grad dadd_init_attn_grad_bf16
 
 // C entry points (include/dadd_hip.h)
 #define dadd_conv_igemm_f16 dadd_conv_igemm_bf16
@@ -65,3 +69,6 @@
 #define dadd_layernorm_grad_f16 dadd_layernorm_grad_bf16
 #define dadd_geglu_f16 dadd_geglu_bf16
 #define dadd_geglu_grad_f16 dadd_geglu_grad_bf16
+
+// C entry points (include/dadd_hip_attn_grad.h)
+#define dadd_attn_grad_f16 dadd_attn_grad_bf16

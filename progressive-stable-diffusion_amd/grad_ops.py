@@ -1,13 +1,17 @@
-"""Differentiable Linear / conv3x3, GroupNorm(+SiLU), LayerNorm and GEGLU on the HIP kernels: the operators of a training
-step and their gradients.
+"""Differentiable Linear / conv3x3, GroupNorm(+SiLU), LayerNorm, GEGLU and attention (self, general and the triple-pathway
+cross-attention) on the HIP kernels: the operators of a training step and their gradients.
 
 Matrix products: forward is ``HipBackend.igemm``; the data gradient is the same kernel on ``dy`` with the weight re-laid
 by ``dgrad_weight``; the weight and bias gradients are the M-reduction GEMM of ``HipBackend.wgrad`` (csrc/wgrad.hip).
 Norms and gating: forward is ``HipBackend.groupnorm`` / ``layernorm`` / ``geglu``, backward the reduction kernels of
 csrc/norm_grad.hip (``groupnorm_grad`` / ``layernorm_grad`` / ``geglu_grad``), which recompute the statistics from the
-saved input.  With these a ResnetBlock2D and a transformer feed-forward are differentiable end to end.
-These are operators, not the training loop: attention has no backward yet, and neither do the strided / upsampled data
-gradient and the 4-channel end convolutions.
+saved input.  Attention: forward is ``HipBackend.self_attn`` / ``attention`` / ``tri_xattn``, backward the three launches
+of csrc/attn_grad.hip (``attn_grad``: row statistics recomputed from q, k, v and dy, then dK / dV, then dQ); the
+triple-pathway gradient is composed from it, one call per pathway with the gate or lambda as the scale of dy.
+With these a ResnetBlock2D and a full BasicTransformerBlock (attn1, attn2, feed-forward) are differentiable end to end.
+These are operators, not the training loop: still missing are the strided / upsampled data gradient, the 4-channel end
+convolutions, the optimizer, the wiring into ``training_step`` and attention head dims other than 40 / 80 / 160
+(DESIGN.md §7.1).
 
 Operands: ``x`` is a 16-bit (fp16 or bf16) NHWC / token-major tensor on the backend's device, ``w`` the **fp32 master**
 weight in the library layout ``[N][taps*C]`` (``[Cout][ky][kx][Cin]`` flattened), ``bias`` / ``gamma`` / ``beta`` fp32.
@@ -227,6 +231,164 @@ class _Geglu(torch.autograd.Function):
         be.geglu_grad(h, dy, dh)
         be.release_to_current()
         return dh, None
+
+
+def _attn_ws(be, q, heads):
+    return be.empty((be.attn_grad_ws_numel(q.shape[0], heads, q.shape[1]),), torch.float32)
+
+
+class _SelfAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, be, heads):
+        _check16(qkv, "qkv")
+        if qkv.dim() != 3 or qkv.shape[-1] % (3 * heads):
+            raise ValueError(f"self_attention takes qkv [B,N,3C] with C a multiple of heads = {heads}, got {tuple(qkv.shape)}")
+        qkv = qkv.contiguous()
+        b, n, c3 = qkv.shape
+        be.wait_current()
+        out = be.empty((b, n, c3 // 3), qkv.dtype)
+        be.self_attn(qkv, out, heads)
+        be.release_to_current()
+        ctx.save_for_backward(qkv)
+        ctx.be, ctx.heads = be, heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (qkv,) = ctx.saved_tensors
+        be, heads = ctx.be, ctx.heads
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        c = qkv.shape[-1] // 3
+        dy = dy.to(qkv.dtype).contiguous()
+        be.wait_current()
+        dqkv = be.empty(tuple(qkv.shape), qkv.dtype)
+        q, k, v = (qkv[..., i * c:(i + 1) * c] for i in range(3))
+        be.attn_grad(q, k, v, dy, dq=dqkv[..., :c], dk=dqkv[..., c:2 * c], dv=dqkv[..., 2 * c:], ws=_attn_ws(be, q, heads),
+                     heads=heads)
+        be.release_to_current()
+        return dqkv, None, None
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, be, heads):
+        for t, what in ((q, "q"), (k, "k"), (v, "v")):
+            _check16(t, what)
+        if not (q.dim() == k.dim() == v.dim() == 3 and k.shape == v.shape and q.shape[0] == k.shape[0]
+                and q.shape[2] == k.shape[2] and q.dtype == k.dtype == v.dtype) or q.shape[2] % heads:
+            raise ValueError(f"attention takes q [B,Nq,C] and k, v [B,Nk,C] of one 16-bit type, got {tuple(q.shape)} "
+                             f"{tuple(k.shape)} {tuple(v.shape)}")
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        be.wait_current()
+        out = be.empty(tuple(q.shape), q.dtype)
+        be.attention(q, k, v, out, heads)
+        be.release_to_current()
+        ctx.save_for_backward(q, k, v)
+        ctx.be, ctx.heads = be, heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        q, k, v = ctx.saved_tensors
+        be, heads = ctx.be, ctx.heads
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        if not (need_q or need_k or need_v):
+            return (None,) * 5
+        dy = dy.to(q.dtype).contiguous()
+        be.wait_current()
+        dq = be.empty(tuple(q.shape), q.dtype) if need_q else None
+        dk = be.empty(tuple(k.shape), q.dtype) if need_k else None
+        dv = be.empty(tuple(v.shape), q.dtype) if need_v else None
+        be.attn_grad(q, k, v, dy, dq=dq, dk=dk, dv=dv, ws=_attn_ws(be, q, heads), heads=heads)
+        be.release_to_current()
+        return dq, dk, dv, None, None
+
+
+class _TriCrossAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, kv, gates, be, lam, heads, mode):
+        _check16(q, "q")
+        c = q.shape[-1]
+        want = (48, 4 * c) if mode == L.XATTN_SPLIT else (32, 2 * c)
+        if mode not in (L.XATTN_SPLIT, L.XATTN_BASELINE) or q.dim() != 3 or kv.dtype != q.dtype \
+                or kv.shape != (q.shape[0],) + want or c % heads:
+            raise ValueError(f"tri_cross_attention takes q [B,N,C] and kv [B,{want[0]},{want[1] // c}C] of q's type in mode "
+                             f"{mode}, got {tuple(q.shape)} and {tuple(kv.shape)} {kv.dtype}")
+        if mode == L.XATTN_SPLIT and (gates is None or gates.dtype != torch.float32 or gates.numel() != 2):
+            raise ValueError("tri_cross_attention: split mode takes gates, a device fp32[2] buffer")
+        q, kv = q.contiguous(), kv.contiguous()
+        gates = None if gates is None else gates.contiguous()
+        be.wait_current()
+        out = be.empty(tuple(q.shape), q.dtype)
+        be.tri_xattn(q, kv, out, gates, lam, mode, heads)
+        be.release_to_current()
+        ctx.save_for_backward(q, kv, gates)
+        ctx.be, ctx.cfg = be, (lam, heads, mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        q, kv, gates = ctx.saved_tensors
+        be, (lam, heads, mode) = ctx.be, ctx.cfg
+        need_q, need_kv = ctx.needs_input_grad[:2]
+        if not (need_q or need_kv):
+            return (None,) * 7
+        c = q.shape[-1]
+        dy = dy.to(q.dtype).contiguous()
+        # (first token, tokens, first column of K; V follows K) and the scale of dy of every pathway
+        if mode == L.XATTN_SPLIT:
+            paths = [(16, 16, 0, 1.0, gates[0:1]), (0, 16, 2 * c, 1.0, gates[1:2])]     # anatomy, disease
+            if lam != 0.0:
+                paths.append((32, 16, 2 * c, float(lam), None))                          # delta, skipped as in the forward
+        else:
+            paths = [(0, 32, 0, 1.0, None)]
+        be.wait_current()
+        dkv = be.zeros(tuple(kv.shape), kv.dtype) if need_kv else None
+        ws = _attn_ws(be, q, heads)
+        dqs = []
+        for t0, nt, kc, scale, scale_dev in paths:
+            k, v = kv[:, t0:t0 + nt, kc:kc + c], kv[:, t0:t0 + nt, kc + c:kc + 2 * c]
+            dq = be.empty(tuple(q.shape), q.dtype) if need_q else None
+            dk = dkv[:, t0:t0 + nt, kc:kc + c] if need_kv else None
+            dv = dkv[:, t0:t0 + nt, kc + c:kc + 2 * c] if need_kv else None
+            be.attn_grad(q, k, v, dy, dq=dq, dk=dk, dv=dv, ws=ws, heads=heads, do_scale=scale, do_scale_dev=scale_dev)
+            dqs.append(dq)
+        dq = None
+        if need_q:
+            dq = dqs[0]
+            if len(dqs) > 1:
+                with be.ctx():      # fp32 sum of the pathways' dq, rounded once
+                    acc = dqs[0].float()
+                    for t in dqs[1:]:
+                        acc += t.float()
+                    dq = acc.to(q.dtype)
+        be.release_to_current()
+        return dq, dkv, None, None, None, None, None
+
+
+def self_attention(be, qkv, heads):
+    """qkv [B,N,3C] (q | k | v blocks of C columns) -> softmax(q k^T / sqrt(d)) v [B,N,C] per head; differentiable in qkv:
+    the backward is one ``attn_grad`` call that writes dq, dk and dv into the column blocks of one [B,N,3C] tensor.
+    The backward takes d = C / heads in {40, 80, 160} and N a multiple of 16."""
+    return _SelfAttention.apply(qkv, be, int(heads))
+
+
+def attention(be, q, k, v, heads):
+    """softmax(q k^T / sqrt(d)) v with separate lengths: q [B,Nq,C], k, v [B,Nk,C] -> [B,Nq,C]; differentiable in q, k and
+    v (only the gradients that are needed are computed).  Backward: d in {40, 80, 160}, Nq and Nk multiples of 16."""
+    return _Attention.apply(q, k, v, be, int(heads))
+
+
+def tri_cross_attention(be, q, kv, gates, lam, heads, mode=L.XATTN_SPLIT):
+    """The triple-pathway cross-attention of ``HipBackend.tri_xattn``: q [B,N,C] against kv [B,48,4C] (split mode: anatomy,
+    disease and delta pathways of 16 tokens with independent softmaxes, weighted by ``gates`` (device fp32[2]) and the
+    python float ``lam``) or kv [B,32,2C] (baseline mode: one softmax over 32 tokens).  Differentiable in q and kv; the
+    gates and lambda are not learnable in the reference model and get no gradient.  The backward is one ``attn_grad``
+    call per pathway on the pathway's slice of kv (the delta pathway is skipped when ``lam == 0``, as in the forward) with
+    the gate (read on the device) or lambda as the scale of dy; dq is the fp32 sum of the pathways' dq, dkv is zero
+    outside the slices the pathways read."""
+    return _TriCrossAttention.apply(q, kv, gates, be, float(lam), int(heads), int(mode))
 
 
 def group_norm(be, x, gamma, beta, groups=32, eps=1e-5, silu=False, x2=None):

@@ -20,7 +20,9 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            # training backward: the M-reduction GEMM of the weight gradient and its bf16 twin
            "wgrad.hip", "wgrad_bf16.hip",
            # training backward: GroupNorm(+SiLU) / LayerNorm / GEGLU and the plain GEGLU forward, and their bf16 twin
-           "norm_grad.hip", "norm_grad_bf16.hip")
+           "norm_grad.hip", "norm_grad_bf16.hip",
+           # training backward: attention (statistics, dK / dV, dQ) and its bf16 twin
+           "attn_grad.hip", "attn_grad_bf16.hip")
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -64,6 +66,14 @@ class GnGradDesc(C.Structure):
     """Mirror of ``dadd_gn_grad_desc``."""
     _fields_ = [(n, vp) for n in ("x1", "x2", "dy", "gamma", "beta", "dx1", "dx2", "dgamma", "dbeta", "ws")] + \
                [(n, i32) for n in ("B", "HW", "C1", "C2", "groups", "silu")] + [("eps", f32)]
+
+
+class AttnGradDesc(C.Structure):
+    """Mirror of ``dadd_attn_grad_desc``."""
+    _fields_ = [(n, vp) for n in ("q", "k", "v", "dout", "dq", "dk", "dv", "ws", "do_scale_dev")] + \
+               [(n, i64) for n in ("bs_q", "bs_kv", "bs_do", "bs_dq", "bs_dkv")] + \
+               [(n, i32) for n in ("B", "Nq", "Nk", "heads", "d", "ld_q", "ld_kv", "ld_do", "ld_dq", "ld_dkv")] + \
+               [("do_scale", f32)]
 
 
 # name -> (restype, argtypes); every symbol include/dadd_hip.h declares
@@ -157,6 +167,13 @@ NORM_GRAD_PROTOTYPES = {
     "dadd_geglu_grad_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
 }
 
+# every symbol include/dadd_hip_attn_grad.h declares (training backward of attention, csrc/attn_grad.hip)
+ATTN_GRAD_PROTOTYPES = {
+    "dadd_attn_grad_f16": (C.c_int, [C.POINTER(AttnGradDesc), vp]),
+    "dadd_attn_grad_bf16": (C.c_int, [C.POINTER(AttnGradDesc), vp]),
+    "dadd_attn_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -165,7 +182,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
-        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h")]
+        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
+                                                                       "dadd_hip_attn_grad.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -191,7 +209,8 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension is required (run __graft_entry__.build()); "
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES}.items():
+    for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
+                              **ATTN_GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
