@@ -499,6 +499,54 @@ class HipBackend:
         d.do_scale = float(do_scale)
         L.check(fn(C.byref(d), self.s))
 
+    # -- the optimizer step (csrc/optim.hip); optim.FusedAdamW is the owner of these buffers
+    @staticmethod
+    def _optim_flat(t, what, n=None, dtype=torch.float32):
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+            raise ValueError(f"optim: {what} must be a flat contiguous {dtype} tensor" + (f" of {n} elements" if n else "") +
+                             f", got {tuple(t.shape)} {t.dtype}")
+
+    def optim_grad_stats(self, g, partials, flags, *, max_blocks=0):
+        """One pass over the flat fp32 gradient ``g`` (a multiple of ``lib.OPTIM_CHUNK`` elements): ``partials`` [chunks]
+        fp32 = sum of g^2 per chunk, ``flags`` [chunks] int32 = 1 where a chunk holds an inf or NaN.  Fixed summation order,
+        the result does not depend on ``max_blocks`` (the cap of the grid; 0 = the kernel's default)."""
+        n = g.numel()
+        if n == 0 or n % L.OPTIM_CHUNK:
+            raise ValueError(f"optim_grad_stats: {n} elements is not a positive multiple of the chunk {L.OPTIM_CHUNK}")
+        self._optim_flat(g, "g")
+        self._optim_flat(partials, "partials", n // L.OPTIM_CHUNK)
+        self._optim_flat(flags, "flags", n // L.OPTIM_CHUNK, torch.int32)
+        L.check(self.lib.dadd_optim_grad_stats(_p(g), n, _p(partials), _p(flags), int(max_blocks), self.s))
+
+    def optim_finalize(self, partials, flags, state):
+        """One workgroup: from the chunk partials and flags to the norm, the clip coefficient, the step count, the
+        per-group constants and the loss scale in ``state`` (int32 words of ``lib.OptimState``), all on the device."""
+        self._optim_flat(partials, "partials")
+        self._optim_flat(flags, "flags", partials.numel(), torch.int32)
+        self._optim_flat(state, "state", C.sizeof(L.OptimState) // 4, torch.int32)
+        L.check(self.lib.dadd_optim_finalize(_p(partials), _p(flags), partials.numel(), _p(state), self.s))
+
+    def optim_adamw_step(self, p, g, m, v, state, group_chunks, *, ema=None, p16=None, ema_weight=0.0, flags=0, max_blocks=0):
+        """The fused AdamW pass over the flat fp32 arrays ``p, g, m, v`` with the constants ``optim_finalize`` left in
+        ``state``; ``group_chunks``: chunks per group (a sequence or a ctypes int array).  ``flags`` (``lib.OPTIM_*``)
+        select the EMA update into ``ema`` (weight ``ema_weight`` = 1 - decay), the 16-bit copy into ``p16`` (its dtype
+        must match the flag) and the zeroing of ``g``."""
+        n = p.numel()
+        for t, what in ((p, "p"), (g, "g"), (m, "m"), (v, "v")) + (((ema, "ema"),) if ema is not None else ()):
+            self._optim_flat(t, what, n)
+        self._optim_flat(state, "state", C.sizeof(L.OptimState) // 4, torch.int32)
+        want16 = {L.OPTIM_P16_F16: torch.float16, L.OPTIM_P16_BF16: torch.bfloat16}.get(flags & (L.OPTIM_P16_F16 | L.OPTIM_P16_BF16))
+        if (p16 is None) != (want16 is None) or (p16 is not None and flags & L.OPTIM_P16_F16 and flags & L.OPTIM_P16_BF16):
+            raise ValueError("optim_adamw_step: p16 goes with exactly one of OPTIM_P16_F16 / OPTIM_P16_BF16")
+        if p16 is not None:
+            self._optim_flat(p16, "p16", n, want16)
+        if bool(flags & L.OPTIM_EMA) != (ema is not None):
+            raise ValueError("optim_adamw_step: ema goes with OPTIM_EMA")
+        if not isinstance(group_chunks, C.Array):
+            group_chunks = (C.c_int * len(group_chunks))(*group_chunks)
+        L.check(self.lib.dadd_optim_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(p16), n, group_chunks, len(group_chunks),
+                                               _p(state), float(ema_weight), int(flags), int(max_blocks), self.s))
+
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""
         b, n, c3 = qkv.shape

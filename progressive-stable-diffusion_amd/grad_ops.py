@@ -10,8 +10,10 @@ of csrc/attn_grad.hip (``attn_grad``: row statistics recomputed from q, k, v and
 triple-pathway gradient is composed from it, one call per pathway with the gate or lambda as the scale of dy.
 With these a ResnetBlock2D and a full BasicTransformerBlock (attn1, attn2, feed-forward) are differentiable end to end.
 These are operators, not the training loop: still missing are the strided / upsampled data gradient, the 4-channel end
-convolutions, the optimizer, the wiring into ``training_step`` and attention head dims other than 40 / 80 / 160
-(DESIGN.md §7.1).
+convolutions, the wiring into ``training_step`` and attention head dims other than 40 / 80 / 160.  The
+optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
+arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
+in the arena's flat gradient buffer).
 
 Operands: ``x`` is a 16-bit (fp16 or bf16) NHWC / token-major tensor on the backend's device, ``w`` the **fp32 master**
 weight in the library layout ``[N][taps*C]`` (``[Cout][ky][kx][Cin]`` flattened), ``bias`` / ``gamma`` / ``beta`` fp32.

@@ -22,7 +22,9 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            # training backward: GroupNorm(+SiLU) / LayerNorm / GEGLU and the plain GEGLU forward, and their bf16 twin
            "norm_grad.hip", "norm_grad_bf16.hip",
            # training backward: attention (statistics, dK / dV, dQ) and its bf16 twin
-           "attn_grad.hip", "attn_grad_bf16.hip")
+           "attn_grad.hip", "attn_grad_bf16.hip",
+           # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (one source, no bf16 twin)
+           "optim.hip")
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -174,6 +176,33 @@ ATTN_GRAD_PROTOTYPES = {
     "dadd_attn_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
 }
 
+# include/dadd_hip_optim.h: the optimizer step (csrc/optim.hip)
+OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8
+OPTIM_EMA, OPTIM_P16_F16, OPTIM_P16_BF16, OPTIM_ZERO_GRAD = 1, 2, 4, 8
+
+
+class OptimGroup(C.Structure):
+    """Mirror of ``dadd_optim_group``."""
+    _fields_ = [(n, f32) for n in ("beta1", "beta2", "eps", "weight_decay", "one_minus_beta1", "one_minus_beta2",
+                                   "decay", "step_size", "rsqrt_bc2")] + [("reserved", f32 * 3)]
+
+
+class OptimState(C.Structure):
+    """Mirror of ``dadd_optim_state``, the device-resident block of one optimizer."""
+    _fields_ = [(n, i32) for n in ("step", "found_inf", "growth_tracker", "growth_interval", "n_groups")] + \
+               [("reserved_i", i32 * 3)] + \
+               [(n, f32) for n in ("grad_norm", "coef", "scale", "max_norm", "growth_factor", "backoff_factor")] + \
+               [("reserved_f", f32 * 2), ("lr", f32 * OPTIM_MAX_GROUPS), ("group", OptimGroup * OPTIM_MAX_GROUPS)]
+
+
+# every symbol include/dadd_hip_optim.h declares
+OPTIM_PROTOTYPES = {
+    "dadd_optim_grad_stats": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_int, vp]),
+    "dadd_optim_finalize": (C.c_int, [vp, vp, C.c_longlong, vp, vp]),
+    "dadd_optim_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_longlong, C.POINTER(C.c_int), C.c_int, vp, f32,
+                                        C.c_int, C.c_int, vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -183,7 +212,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
         [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
-                                                                       "dadd_hip_attn_grad.h")]
+                                                                       "dadd_hip_attn_grad.h", "dadd_hip_optim.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -210,7 +239,7 @@ def load() -> C.CDLL:
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
-                              **ATTN_GRAD_PROTOTYPES}.items():
+                              **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,6 +1,7 @@
 """``LinearWarmupCosineAnnealingLR`` as a pure function of the epoch (src/models/lr_scheduler.py:14-64): linear warm-up
 from ``warmup_start_lr`` to the base rate over ``warmup_epochs``, then a cosine decay to ``eta_min`` at ``max_epochs``.
-The optimizer it would drive (fused AdamW over four parameter groups) is not built yet."""
+The optimizer it drives is ``optim.FusedAdamW`` (fused AdamW over the reference's four parameter groups):
+``FusedAdamW.set_lrs(warmup_cosine_lr(...))`` takes the list as it is."""
 from __future__ import annotations
 
 import math

@@ -1,0 +1,363 @@
+"""The optimizer of a training step on the HIP kernels of csrc/optim.hip (include/dadd_hip_optim.h): AdamW over parameter
+groups with global-norm gradient clipping, a loss scale with skip-on-overflow (``precision: 16-mixed``), the EMA of the
+weights, the 16-bit working copy of the weights and the zeroing of the gradients.  One step is three launches (gradient
+statistics, one workgroup of scalar work, one fused pass over the parameters) and no host synchronisation.
+
+``ParamArena`` owns the flat fp32 buffers the kernels work on: master weights ``p``, gradients ``g``, the moments ``m``
+and ``v``, optionally the EMA and the 16-bit copy ``p16``.  It is plain torch and lives on any device.  ``FusedAdamW``
+owns the device-resident state block (step count, loss scale, per-group constants) and launches the kernels.
+``reference_param_groups`` restates the grouping of the reference's ``configure_optimizers`` (src/models/
+diffusion_module_ip.py: UNet and ordinal embedder at ``lr``, image projection and feature purifier at ``2 * lr``).
+
+Not wired into ``DiffusionModuleWithIP`` yet: ``configure_optimizers()`` still raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import OrderedDict
+from typing import Dict, List, Mapping, Optional, Sequence
+
+import torch
+
+from . import lib as L
+
+CHUNK = L.OPTIM_CHUNK
+_ALIGN = 8          # elements: 32 bytes of fp32, 16 bytes of the 16-bit copy
+_P16_FLAG = {torch.float16: L.OPTIM_P16_F16, torch.bfloat16: L.OPTIM_P16_BF16}
+
+
+def _round_up(x: int, to: int) -> int:
+    return -(-x // to) * to
+
+
+class ParamArena:
+    """Flat fp32 storage of a set of named parameters, laid out group by group.
+
+    ``tensors``: ordered mapping name -> fp32 tensor (the initial values; copied).  ``group_of``: name -> group index.
+    Every tensor starts on a multiple of 8 elements, so its fp32 view and its 16-bit view are both 16-byte aligned;
+    every group is padded to a multiple of ``CHUNK`` elements, so one workgroup of the kernels never sees two groups.
+    The padding is zero in every array and stays zero under the update (zero gradient, zero moments: the update term is
+    0 / (0 + eps)).  ``names`` is the arena order: group 0's tensors in mapping order, then group 1's, ...
+    """
+
+    def __init__(self, tensors: Mapping[str, torch.Tensor], group_of: Mapping[str, int], *, device=None,
+                 working_dtype: Optional[torch.dtype] = None, ema: bool = False):
+        if not tensors:
+            raise ValueError("ParamArena needs at least one tensor")
+        for k, t in tensors.items():
+            if t.dtype != torch.float32:
+                raise ValueError(f"{k}: the arena holds fp32 masters, got {t.dtype}")
+            if k not in group_of or int(group_of[k]) < 0:
+                raise ValueError(f"{k}: no group index")
+        self.n_groups = max(int(group_of[k]) for k in tensors) + 1
+        if self.n_groups > L.OPTIM_MAX_GROUPS:
+            raise ValueError(f"{self.n_groups} groups, the kernels take {L.OPTIM_MAX_GROUPS}")
+        self.device = torch.device(device) if device is not None else next(iter(tensors.values())).device
+        self.names: List[str] = []
+        self.shapes: Dict[str, torch.Size] = {}
+        self.offsets: Dict[str, int] = {}
+        self.group_of: Dict[str, int] = {}
+        self.group_names: List[List[str]] = [[] for _ in range(self.n_groups)]
+        self.group_start: List[int] = []
+        self.group_chunks: List[int] = []
+        off = 0
+        for gi in range(self.n_groups):
+            self.group_start.append(off)
+            for k, t in tensors.items():
+                if int(group_of[k]) != gi:
+                    continue
+                off = _round_up(off, _ALIGN)
+                self.names.append(k)
+                self.shapes[k], self.offsets[k], self.group_of[k] = t.shape, off, gi
+                self.group_names[gi].append(k)
+                off += t.numel()
+            off = _round_up(off, CHUNK)
+            self.group_chunks.append((off - self.group_start[gi]) // CHUNK)
+        self.numel = off
+        self.n_chunks = off // CHUNK
+
+        def flat():
+            return torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        self.p, self.g, self.m, self.v = flat(), flat(), flat(), flat()
+        self.ema: Optional[torch.Tensor] = None
+        self.p16: Optional[torch.Tensor] = None
+        with torch.no_grad():
+            for k in self.names:
+                self._view(self.p, k).copy_(tensors[k])
+        if ema:
+            self.ensure_ema()
+        if working_dtype is not None:
+            self.ensure_p16(working_dtype)
+
+    # -- optional arrays
+    def ensure_ema(self) -> torch.Tensor:
+        """Allocate the EMA (a copy of the current weights) unless it exists."""
+        if self.ema is None:
+            self.ema = self.p.clone()
+        return self.ema
+
+    def ensure_p16(self, dtype: torch.dtype) -> torch.Tensor:
+        """Allocate the 16-bit working copy (the current weights, rounded) unless it exists; the type is fixed then."""
+        if dtype not in _P16_FLAG:
+            raise ValueError(f"the working copy is fp16 or bf16, not {dtype}")
+        if self.p16 is None:
+            self.p16 = self.p.to(dtype)
+        elif self.p16.dtype != dtype:
+            raise ValueError(f"the arena's working copy is {self.p16.dtype}, not {dtype}")
+        return self.p16
+
+    # -- views
+    def _view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
+        off, shape = self.offsets[name], self.shapes[name]
+        return flat[off:off + shape.numel()].view(shape)
+
+    def param(self, name: str) -> torch.Tensor:
+        """fp32 master weight, a view of ``p`` in the tensor's own shape."""
+        return self._view(self.p, name)
+
+    def grad(self, name: str) -> torch.Tensor:
+        return self._view(self.g, name)
+
+    def param16(self, name: str) -> torch.Tensor:
+        """The 16-bit working copy the optimizer step refreshes: what a forward kernel reads instead of casting."""
+        if self.p16 is None:
+            raise RuntimeError("the arena has no 16-bit working copy (working_dtype / ensure_p16)")
+        return self._view(self.p16, name)
+
+    def exp_avg(self, name: str) -> torch.Tensor:
+        return self._view(self.m, name)
+
+    def exp_avg_sq(self, name: str) -> torch.Tensor:
+        return self._view(self.v, name)
+
+    def ema_param(self, name: str) -> torch.Tensor:
+        if self.ema is None:
+            raise RuntimeError("the arena has no EMA (ema=True / ensure_ema)")
+        return self._view(self.ema, name)
+
+    def attach(self, params: Mapping[str, torch.Tensor]) -> None:
+        """Make each given leaf tensor a view of ``p`` with ``.grad`` preset to the matching view of ``g``: autograd
+        then accumulates in place into the arena (torch adds into an existing ``.grad``), which is gradient
+        accumulation over micro-batches and leaves one flat gradient buffer.  The tensor's current values are dropped:
+        the arena's are the truth."""
+        for k, t in params.items():
+            if k not in self.offsets:
+                raise KeyError(f"{k} is not in the arena")
+            if not t.is_leaf or t.shape != self.shapes[k] or t.dtype != torch.float32:
+                raise ValueError(f"{k}: expected an fp32 leaf of shape {tuple(self.shapes[k])}, got {tuple(t.shape)} {t.dtype}")
+            t.data = self.param(k)
+            t.grad = self.grad(k)
+
+
+def reference_param_groups(names: Sequence[str], lr: float, weight_decay: float = 0.0) -> List[dict]:
+    """The reference's four parameter groups over state-dict key names: ``unet.`` and ``ordinal_embedder.`` at ``lr``,
+    ``image_projection.`` and ``feature_purifier.`` at ``2 * lr`` (left out when no key has that prefix), all with the
+    one ``weight_decay``.  ``vae.`` and ``image_encoder.`` are frozen in the reference and excluded; any other key is an
+    error.  -> list of ``{"name", "params", "lr", "weight_decay"}`` in that order."""
+    spec = (("unet.", 1.0, False), ("ordinal_embedder.", 1.0, False), ("image_projection.", 2.0, False),
+            ("feature_purifier.", 2.0, True))
+    frozen = ("vae.", "image_encoder.")
+    buckets: "OrderedDict[str, List[str]]" = OrderedDict((pre, []) for pre, _, _ in spec)
+    for k in names:
+        if k.startswith(frozen):
+            continue
+        for pre in buckets:
+            if k.startswith(pre):
+                buckets[pre].append(k)
+                break
+        else:
+            raise ValueError(f"{k}: no parameter group takes this key")
+    return [{"name": pre[:-1], "params": buckets[pre], "lr": mult * lr, "weight_decay": weight_decay}
+            for pre, mult, optional in spec if buckets[pre] or not optional]
+
+
+def arena_from_groups(tensors: Mapping[str, torch.Tensor], groups: Sequence[dict], **kw) -> ParamArena:
+    """``ParamArena`` over the tensors that ``groups`` (``reference_param_groups``' list) names, group k = groups[k]."""
+    group_of = {k: gi for gi, g in enumerate(groups) for k in g["params"]}
+    return ParamArena(OrderedDict((k, tensors[k]) for g in groups for k in g["params"]), group_of, **kw)
+
+
+class FusedAdamW:
+    """AdamW over a ``ParamArena`` on the kernels of csrc/optim.hip.
+
+    ``groups``: one ``{"lr", "weight_decay"}`` per arena group (further keys are ignored, so the list of
+    ``reference_param_groups`` passes as it is).  ``max_grad_norm`` > 0 clips by the global norm
+    (``clip_grad_norm_``'s rule); ``init_scale`` > 0 switches the loss scale on: the gradients in the arena are then
+    taken to be ``scale`` times the true ones, a step with a non-finite gradient is skipped and halves the scale, and
+    ``growth_interval`` clean steps double it (torch.amp.GradScaler).  The caller multiplies its loss by ``scale()``'s
+    tensor (a device scalar, no sync).  ``ema_decay`` allocates the arena's EMA; ``working_dtype`` its 16-bit copy
+    (default: what the arena already has).  ``be=None`` gives an optimizer that holds state but cannot step (CPU).
+    """
+
+    def __init__(self, be, arena: ParamArena, groups: Sequence[Mapping], *, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: float = 0.0, ema_decay: Optional[float] = None,
+                 working_dtype: Optional[torch.dtype] = None, init_scale: float = 0.0, growth_interval: int = 2000,
+                 growth_factor: float = 2.0, backoff_factor: float = 0.5, max_blocks: int = 0):
+        if len(groups) != arena.n_groups:
+            raise ValueError(f"{len(groups)} groups for an arena of {arena.n_groups}")
+        if be is not None and arena.device != be.device:
+            raise ValueError(f"the arena lives on {arena.device}, the backend on {be.device}")
+        self.be, self.arena = be, arena
+        self.max_blocks = int(max_blocks)
+        self.ema_decay = ema_decay
+        if ema_decay is not None:
+            arena.ensure_ema()
+        if working_dtype is not None:
+            arena.ensure_p16(working_dtype)
+        self.betas = [tuple(float(b) for b in g.get("betas", betas)) for g in groups]
+        host = L.OptimState()
+        host.n_groups, host.growth_interval = arena.n_groups, int(growth_interval)
+        host.scale, host.max_norm = float(init_scale), float(max_grad_norm)
+        host.growth_factor, host.backoff_factor = float(growth_factor), float(backoff_factor)
+        for k, g in enumerate(groups):
+            b1, b2 = self.betas[k]
+            hg = host.group[k]
+            host.lr[k] = float(g["lr"])
+            hg.beta1, hg.beta2, hg.eps, hg.weight_decay = b1, b2, float(g.get("eps", eps)), float(g["weight_decay"])
+            hg.one_minus_beta1, hg.one_minus_beta2 = 1.0 - b1, 1.0 - b2
+        self._words = C.sizeof(L.OptimState) // 4
+        self.state = torch.zeros(self._words, dtype=torch.int32, device=arena.device)
+        self._upload(host)
+        self.partials = torch.empty(arena.n_chunks, dtype=torch.float32, device=arena.device)
+        self.flags = torch.empty(arena.n_chunks, dtype=torch.int32, device=arena.device)
+        self._group_chunks = (C.c_int * arena.n_groups)(*arena.group_chunks)
+        self._lr_words = self.state[L.OptimState.lr.offset // 4:L.OptimState.lr.offset // 4 + arena.n_groups].view(torch.float32)
+        self._scale_word = self.state[L.OptimState.scale.offset // 4:L.OptimState.scale.offset // 4 + 1].view(torch.float32)
+
+    # -- the state block
+    def _upload(self, host: "L.OptimState") -> None:
+        words = torch.frombuffer(bytearray(bytes(host)), dtype=torch.int32)
+        if self.be is not None:
+            self.be.wait_current()          # the block (and the moments a load wrote) were produced on torch's stream
+            self.be.copy_(self.state, words)
+        else:
+            self.state.copy_(words)
+
+    def _download(self) -> "L.OptimState":
+        if self.be is not None:
+            self.be.synchronize()
+        return L.OptimState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+
+    def set_lrs(self, lrs: Sequence[float]) -> None:
+        """The learning rates of the next step, one per group (``lr_scheduler.warmup_cosine_lr``'s list): one small copy
+        into the state block, ordered on the backend's stream."""
+        if len(lrs) != self.arena.n_groups:
+            raise ValueError(f"{len(lrs)} learning rates for {self.arena.n_groups} groups")
+        src = torch.tensor([float(x) for x in lrs], dtype=torch.float32)
+        if self.be is not None:
+            self.be.copy_(self._lr_words, src)
+        else:
+            self._lr_words.copy_(src)
+
+    def scale(self) -> torch.Tensor:
+        """The loss scale as a one-element device tensor (a view of the state block; 0 = no loss scaling)."""
+        return self._scale_word
+
+    def stats(self) -> dict:
+        """``step, grad_norm, coef, found_inf, scale, growth_tracker`` of the last step.  Synchronises: for logging and
+        tests."""
+        h = self._download()
+        return {"step": h.step, "grad_norm": h.grad_norm, "coef": h.coef, "found_inf": bool(h.found_inf), "scale": h.scale,
+                "growth_tracker": h.growth_tracker}
+
+    # -- the step
+    def _flags(self, update_ema: bool, zero_grad: bool) -> int:
+        a = self.arena
+        if update_ema and (a.ema is None or self.ema_decay is None):
+            raise RuntimeError("update_ema needs ema_decay")
+        return (L.OPTIM_EMA if update_ema else 0) | (_P16_FLAG[a.p16.dtype] if a.p16 is not None else 0) | \
+            (L.OPTIM_ZERO_GRAD if zero_grad else 0)
+
+    def launch(self, update_ema: bool = False, zero_grad: bool = True) -> None:
+        """The three launches on the backend's stream, nothing else: what a graph capture records."""
+        if self.be is None:
+            raise RuntimeError("FusedAdamW was built without a backend: it holds state but cannot step")
+        a, be = self.arena, self.be
+        flags = self._flags(update_ema, zero_grad)
+        be.optim_grad_stats(a.g, self.partials, self.flags, max_blocks=self.max_blocks)
+        be.optim_finalize(self.partials, self.flags, self.state)
+        be.optim_adamw_step(a.p, a.g, a.m, a.v, self.state, self._group_chunks, ema=a.ema if update_ema else None,
+                            p16=a.p16, ema_weight=(1.0 - self.ema_decay) if update_ema else 0.0, flags=flags,
+                            max_blocks=self.max_blocks)
+
+    def step(self, update_ema: bool = False, zero_grad: bool = True) -> None:
+        """One optimizer step on the gradients in the arena: clip, unscale, AdamW, and in the same pass the 16-bit copy,
+        with ``update_ema`` the EMA and with ``zero_grad`` the zeroed gradient.  Ordered after torch's current stream
+        (the backward that produced the gradients) and before what torch's current stream does next; no host sync."""
+        if self.be is None:
+            raise RuntimeError("FusedAdamW was built without a backend: it holds state but cannot step")
+        capturing = self.be._capturing
+        if not capturing:
+            self.be.wait_current()
+        self.launch(update_ema, zero_grad)
+        if not capturing:
+            self.be.release_to_current()
+
+    # -- checkpoints: torch.optim.AdamW's layout
+    def state_dict(self) -> dict:
+        """``{"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...], "scaler": {...}}`` with the
+        parameters numbered in arena order: what ``torch.optim.AdamW.state_dict()`` gives for the same parameters in
+        the same groups (a Lightning checkpoint's ``optimizer_states[0]``), plus the loss scale under ``"scaler"``.
+        ``exp_avg`` / ``exp_avg_sq`` are views of the arena, not copies.  Synchronises."""
+        h, a = self._download(), self.arena
+        state, groups, i = {}, [], 0
+        for gi in range(a.n_groups):
+            idx = []
+            for k in a.group_names[gi]:
+                if h.step > 0:
+                    state[i] = {"step": torch.tensor(float(h.step)), "exp_avg": a.exp_avg(k), "exp_avg_sq": a.exp_avg_sq(k)}
+                idx.append(i)
+                i += 1
+            hg = h.group[gi]
+            groups.append({"lr": float(h.lr[gi]), "betas": self.betas[gi], "eps": float(hg.eps),
+                           "weight_decay": float(hg.weight_decay), "amsgrad": False, "maximize": False, "foreach": None,
+                           "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": True,
+                           "params": idx})
+        return {"state": state, "param_groups": groups,
+                "scaler": {"scale": float(h.scale), "growth_tracker": int(h.growth_tracker)}}
+
+    def load_state_dict(self, sd: Mapping) -> None:
+        """Take moments, step count, learning rates, betas, eps and weight decay from a ``torch.optim.AdamW`` state dict
+        over the same parameters in the same groups (or one of ``state_dict()``); ``"scaler"`` is optional.  The kernels
+        keep one step count for all parameters, so the dict's must agree (parameters without state count as step 0 only
+        when every parameter is without)."""
+        a = self.arena
+        pg = sd["param_groups"]
+        if len(pg) != a.n_groups or any(len(g["params"]) != len(a.group_names[gi]) for gi, g in enumerate(pg)):
+            raise ValueError("param_groups do not match the arena's groups")
+        state = sd["state"]
+        steps = set()
+        names = [k for gi in range(a.n_groups) for k in a.group_names[gi]]
+        order = [i for g in pg for i in g["params"]]
+        with torch.no_grad():
+            for k, i in zip(names, order):
+                st = state.get(i)
+                if st is None:
+                    steps.add(0)
+                    a.exp_avg(k).zero_()
+                    a.exp_avg_sq(k).zero_()
+                    continue
+                steps.add(int(float(st["step"])))
+                if st["exp_avg"].shape != a.shapes[k]:
+                    raise ValueError(f"{k}: exp_avg has shape {tuple(st['exp_avg'].shape)}, the arena {tuple(a.shapes[k])}")
+                a.exp_avg(k).copy_(st["exp_avg"])
+                a.exp_avg_sq(k).copy_(st["exp_avg_sq"])
+        if len(steps) != 1:
+            raise ValueError(f"the parameters carry different step counts {sorted(steps)}; the fused step keeps one")
+        h = self._download()
+        h.step = steps.pop()
+        for gi, g in enumerate(pg):
+            b1, b2 = (float(b) for b in g["betas"])
+            self.betas[gi] = (b1, b2)
+            hg = h.group[gi]
+            h.lr[gi] = float(g["lr"])
+            hg.beta1, hg.beta2, hg.eps, hg.weight_decay = b1, b2, float(g["eps"]), float(g["weight_decay"])
+            hg.one_minus_beta1, hg.one_minus_beta2 = 1.0 - b1, 1.0 - b2
+        if "scaler" in sd:
+            h.scale, h.growth_tracker = float(sd["scaler"]["scale"]), int(sd["scaler"]["growth_tracker"])
+        self._upload(h)
+
+    def ema_state(self) -> "OrderedDict[str, torch.Tensor]":
+        """name -> view of the EMA: the ``state_dict`` a checkpoint stores and ``checkpoint.load_state`` reads with
+        ``which="ema"``."""
+        return OrderedDict((k, self.arena.ema_param(k)) for k in self.arena.names)
