@@ -107,6 +107,7 @@ class HipBackend:
         self.stream = torch.cuda.Stream(device=self.device)
         self._desc = L.IgemmDesc()
         self._wdesc = L.WgradDesc()
+        self._ddesc = L.DgradDesc()
         self._gdesc = L.GnGradDesc()
         self._adesc = L.AttnGradDesc()
         self._n_cu = None
@@ -330,6 +331,27 @@ class HipBackend:
                              "a multiple of 64 (the 4-channel end convolutions have no data gradient here)")
         assert taps in (1, 9) and wt.shape == (dx.shape[-1], taps * n) and dy.is_contiguous() and dx.is_contiguous()
         self.igemm(dy, wt, dx, taps=taps, pad=1 if taps == 9 else 0)
+
+    def dgrad_resample(self, dy, wt, dx, *, stride=1, ups=0):
+        """Data gradient of the stride-2 (``stride=2``) or upsampled (``ups=1``) 3x3 ``igemm``, exactly one of the two:
+        dy [B,Ho,Wo,N] and the re-laid weight wt (``grad_ops.dgrad_weight_stride2`` [C,9N] or ``dgrad_weight_ups``
+        [C,16N]) -> dx [B,Hi,Wi,C], every pixel overwritten (csrc/dgrad.hip).  dy and dx are fp16 or bf16 and may be
+        channel slices of wider tensors: the row strides travel.  One launch, bit-reproducible."""
+        if (stride, int(ups)) not in ((2, 0), (1, 1)):
+            raise ValueError(f"dgrad_resample takes exactly one of stride=2 or ups=1, got stride {stride}, ups {ups}")
+        b, ho, wo, n = dy.shape
+        bx, hi, wi, c = dx.shape
+        t = 16 if ups else 9
+        if bx != b or wt.dim() != 2 or wt.shape != (c, t * n) or not wt.is_contiguous():
+            raise ValueError(f"dgrad_resample: dy {tuple(dy.shape)}, dx {tuple(dx.shape)} take a contiguous wt [{c}, {t}*{n}], "
+                             f"got {tuple(wt.shape)}")
+        fn = getattr(self.lib, "dadd_conv_dgrad_" + _sfx(dy, wt, dx))
+        d = self._ddesc
+        d.dy, d.wt, d.dx = _p(dy), _p(wt), _p(dx)
+        d.B, d.Hi, d.Wi, d.C, d.Ho, d.Wo, d.N = b, hi, wi, c, ho, wo, n
+        d.mode = L.DGRAD_UPS if ups else L.DGRAD_STRIDE2
+        d.ld_dy, d.ld_dx = self._pixel_ld(dy), self._pixel_ld(dx)
+        L.check(fn(C.byref(d), self.s))
 
     def groupnorm(self, x1, x2, gamma, beta, out, ws, groups, eps, silu, ws_chunks=0):
         """``ws_chunks`` > 0: ``ws`` holds the chunk partials written by the producing GEMM's epilogue."""

@@ -36,6 +36,7 @@
 #define attn_grad_stats_kernel attn_grad_stats_kernel_bf16
 #define attn_grad_dkv_kernel attn_grad_dkv_kernel_bf16
 #define attn_grad_dq_kernel attn_grad_dq_kernel_bf16
+#define dgrad_kernel dgrad_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -72,3 +73,6 @@
 
 // C entry points (include/dadd_hip_attn_grad.h)
 #define dadd_attn_grad_f16 dadd_attn_grad_bf16
+
+// C entry points (include/dadd_hip_dgrad.h)
+#define dadd_conv_dgrad_f16 dadd_conv_dgrad_bf16

@@ -3,14 +3,17 @@ cross-attention) on the HIP kernels: the operators of a training step and their 
 
 Matrix products: forward is ``HipBackend.igemm``; the data gradient is the same kernel on ``dy`` with the weight re-laid
 by ``dgrad_weight``; the weight and bias gradients are the M-reduction GEMM of ``HipBackend.wgrad`` (csrc/wgrad.hip).
+The resampling convs (``downsample2d``: stride 2; ``upsample2d``: through a nearest 2x upsample) get their data gradient
+from the gather-GEMM of ``HipBackend.dgrad_resample`` (csrc/dgrad.hip): per parity class of input pixels only the taps
+that reach it, on the weight re-laid by ``dgrad_weight_stride2`` / ``dgrad_weight_ups``.
 Norms and gating: forward is ``HipBackend.groupnorm`` / ``layernorm`` / ``geglu``, backward the reduction kernels of
 csrc/norm_grad.hip (``groupnorm_grad`` / ``layernorm_grad`` / ``geglu_grad``), which recompute the statistics from the
 saved input.  Attention: forward is ``HipBackend.self_attn`` / ``attention`` / ``tri_xattn``, backward the three launches
 of csrc/attn_grad.hip (``attn_grad``: row statistics recomputed from q, k, v and dy, then dK / dV, then dQ); the
 triple-pathway gradient is composed from it, one call per pathway with the gate or lambda as the scale of dy.
 With these a ResnetBlock2D and a full BasicTransformerBlock (attn1, attn2, feed-forward) are differentiable end to end.
-These are operators, not the training loop: still missing are the strided / upsampled data gradient, the 4-channel end
-convolutions, the wiring into ``training_step`` and attention head dims other than 40 / 80 / 160.  The
+These are operators, not the training loop: still missing are the 4-channel end convolutions, the wiring into
+``training_step`` and attention head dims other than 40 / 80 / 160.  The
 optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
 arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
 in the arena's flat gradient buffer).
@@ -36,6 +39,38 @@ def dgrad_weight(w16: torch.Tensor, taps: int) -> torch.Tensor:
     c = w16.shape[1] // taps
     assert w16.dim() == 2 and w16.shape[1] == taps * c
     return w16.reshape(n, taps, c).flip(1).permute(2, 1, 0).reshape(c, taps * n).contiguous()
+
+
+# (ky, kx) of the 9 slabs of ``dgrad_weight_stride2``, in the class order of include/dadd_hip_dgrad.h: the slabs of the
+# parity classes (py, px) = (0,0) | (0,1) | (1,0) | (1,1) of the input pixels, 1 + 2 + 2 + 4 taps.  The resolve table
+# (``first_slab``, ``ntaps``) and the kernel (source pixel (jy + (ky == 0), jx + (kx == 0))) read this order.
+STRIDE2_SLABS = ((1, 1), (1, 0), (1, 2), (0, 1), (2, 1), (0, 0), (0, 2), (2, 0), (2, 2))
+# S(e) for e = -1, 0, 1, 2: the taps of a 3-tap axis that reach input pixel i from row 2i + e of the upsampled output
+UPS_TAP_SETS = ((2,), (1, 2), (0, 1), (0,))
+
+
+def dgrad_weight_stride2(w16: torch.Tensor) -> torch.Tensor:
+    """``[N][9*C] -> [C][9*N]`` for the data gradient of the stride-2 conv (``HipBackend.dgrad_resample(stride=2)``):
+    wt[c][s][n] = w[n][ky_s][kx_s][c] with the slabs s in ``STRIDE2_SLABS`` order, so that the taps of one parity class are
+    one contiguous run of K.  A torch re-layout on the current stream, like ``dgrad_weight``."""
+    n, c = w16.shape[0], w16.shape[1] // 9
+    assert w16.dim() == 2 and w16.shape[1] == 9 * c
+    order = [3 * ky + kx for ky, kx in STRIDE2_SLABS]
+    return w16.reshape(n, 9, c)[:, order].permute(2, 1, 0).reshape(c, 9 * n).contiguous()
+
+
+def dgrad_weight_ups(w16: torch.Tensor) -> torch.Tensor:
+    """``[N][9*C] -> [C][16*N]`` for the data gradient of the upsampled conv (``HipBackend.dgrad_resample(ups=1)``):
+    wt[c][4(e+1) + (f+1)][n] = W4[e][f] = sum of w[n][ky][kx][c] over ky in S(e), kx in S(f) (``UPS_TAP_SETS``), e, f in
+    {-1, 0, 1, 2}: the 36 (tap, phase) products of an input pixel collapse onto 16 source pixels of dy.  A 16-bit weight is
+    summed in fp32 and rounded once to its type (a float32 / float64 weight is summed as it is)."""
+    n, c = w16.shape[0], w16.shape[1] // 9
+    assert w16.dim() == 2 and w16.shape[1] == 9 * c
+    w = w16.reshape(n, 3, 3, c)
+    w = w.float() if w16.dtype in (torch.float16, torch.bfloat16) else w
+    rows = torch.stack([w[:, list(s)].sum(1) for s in UPS_TAP_SETS], 1)          # [n][e][kx][c]
+    w4 = torch.stack([rows[:, :, list(s)].sum(2) for s in UPS_TAP_SETS], 2)      # [n][e][f][c]
+    return w4.permute(3, 1, 2, 0).reshape(c, 16 * n).to(w16.dtype).contiguous()
 
 
 def _forward(be, x, w, bias, taps, stride, ups):
@@ -66,12 +101,18 @@ def _forward(be, x, w, bias, taps, stride, ups):
 def _backward(be, x4, w16, dy, taps, stride, ups, need_dx, need_dw, need_db):
     n, c = w16.shape[0], x4.shape[-1]
     dy4 = dy.contiguous() if taps == 9 else dy.contiguous().reshape(1, 1, -1, n)
-    wt = dgrad_weight(w16, taps) if need_dx else None      # torch plumbing, current stream
+    resample = stride != 1 or ups
+    wt = None
+    if need_dx:                                            # torch plumbing, current stream
+        wt = dgrad_weight(w16, taps) if not resample else dgrad_weight_ups(w16) if ups else dgrad_weight_stride2(w16)
     be.wait_current()
     dx = dw = db = None
     if need_dx:
         dx = be.empty(tuple(x4.shape), x4.dtype)
-        be.dgrad(dy4, wt, dx, taps=taps)
+        if resample:
+            be.dgrad_resample(dy4, wt, dx, stride=stride, ups=int(ups))
+        else:
+            be.dgrad(dy4, wt, dx, taps=taps)
     if need_dw or need_db:
         m = dy4.shape[0] * dy4.shape[1] * dy4.shape[2]
         dw = be.empty((n, taps * c), torch.float32)
@@ -108,7 +149,8 @@ def linear(be, x, w, bias=None):
 
 def conv3x3(be, x, w, bias=None, stride=1, ups=False):
     """3x3 convolution, padding 1, of NHWC ``x`` with ``w`` [N][9*C]; ``stride`` 1 or 2, or ``ups``: through a nearest
-    2x upsample.  Differentiable in w and bias for every form; in x for stride 1 without upsample only."""
+    2x upsample.  Differentiable in w and bias for every form; in x for stride 1 without upsample only: the resampling
+    forms with a data gradient are ``downsample2d`` and ``upsample2d``."""
     if stride not in (1, 2) or (ups and stride != 1) or x.dim() != 4:
         raise ValueError(f"conv3x3 takes NHWC x, stride 1 or 2, or ups with stride 1 (got stride {stride}, ups {ups})")
     if (stride != 1 or ups) and x.requires_grad and torch.is_grad_enabled():
@@ -116,6 +158,26 @@ def conv3x3(be, x, w, bias=None, stride=1, ups=False):
             f"conv3x3(stride={stride}, ups={bool(ups)}) has no data gradient yet: the strided / upsampled dgrad kernel is "
             "missing; pass x.detach() to get the weight and bias gradients")
     return _Product.apply(x, w, bias, be, 9, stride, bool(ups))
+
+
+def downsample2d(be, x, w, bias=None):
+    """diffusers' ``Downsample2D`` conv: 3x3, stride 2, padding 1 of NHWC ``x`` [B,H,W,C] with ``w`` [N][9*C] ->
+    [B,(H-1)//2+1,(W-1)//2+1,N]; odd maps are legal.  Differentiable in x, w and bias: forward and weight / bias gradient
+    are those of ``conv3x3(stride=2)``, the data gradient is the parity-class gather-GEMM of csrc/dgrad.hip on the
+    weight re-laid by ``dgrad_weight_stride2`` (9 tap products per input pixel, none on a zero of a dilated dy)."""
+    if x.dim() != 4:
+        raise ValueError(f"downsample2d takes NHWC x, got {tuple(x.shape)}")
+    return _Product.apply(x, w, bias, be, 9, 2, False)
+
+
+def upsample2d(be, x, w, bias=None):
+    """diffusers' ``Upsample2D``: nearest 2x upsample, then 3x3 conv, padding 1, of NHWC ``x`` [B,H,W,C] with ``w``
+    [N][9*C] -> [B,2H,2W,N]; the upsampled tensor is never materialised.  Differentiable in x, w and bias: forward and
+    weight / bias gradient are those of ``conv3x3(ups=True)``, the data gradient is csrc/dgrad.hip on the 16 pre-summed
+    taps of ``dgrad_weight_ups`` (summed in fp32, rounded once: one rounding more than the forward has)."""
+    if x.dim() != 4:
+        raise ValueError(f"upsample2d takes NHWC x, got {tuple(x.shape)}")
+    return _Product.apply(x, w, bias, be, 9, 1, True)
 
 
 def _check16(x, what):
