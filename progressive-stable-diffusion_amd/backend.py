@@ -108,6 +108,7 @@ class HipBackend:
         self._desc = L.IgemmDesc()
         self._wdesc = L.WgradDesc()
         self._ddesc = L.DgradDesc()
+        self._edesc = L.EndWgradDesc()
         self._gdesc = L.GnGradDesc()
         self._adesc = L.AttnGradDesc()
         self._n_cu = None
@@ -328,9 +329,93 @@ class HipBackend:
         n = dy.shape[-1]
         if n % 64 != 0:
             raise ValueError(f"dgrad contracts over the N = {n} output channels of the forward; the GEMM kernels need "
-                             "a multiple of 64 (the 4-channel end convolutions have no data gradient here)")
+                             "a multiple of 64 (the data gradient of the 4-channel conv_out is dgrad_cout4)")
         assert taps in (1, 9) and wt.shape == (dx.shape[-1], taps * n) and dy.is_contiguous() and dx.is_contiguous()
         self.igemm(dy, wt, dx, taps=taps, pad=1 if taps == 9 else 0)
+
+    # -- training backward of the 4-channel end convs and of the loss (csrc/end_grad.hip)
+    def dgrad_cout4(self, dy_nchw_f32, wt, dx):
+        """Data gradient of ``conv_cout4`` (the UNet's conv_out): dy fp32 NCHW [B,Co<=4,H,W] and the re-laid weight
+        wt [C,9,8] (``grad_ops.dgrad_weight_cout4``: taps flipped, columns >= Co zero) -> dx [B,H,W,C] in wt's 16-bit
+        type.  It is a 4 -> C convolution, so the kernel is ``conv_in_nchw`` without a bias: dy is rounded to the storage
+        type in registers, as the forward rounds the latents."""
+        if dy_nchw_f32.dim() != 4 or dy_nchw_f32.dtype != torch.float32 or not 1 <= dy_nchw_f32.shape[1] <= 4:
+            raise ValueError(f"dgrad_cout4 takes dy fp32 NCHW with 1..4 channels, got {tuple(dy_nchw_f32.shape)} {dy_nchw_f32.dtype}")
+        b, _, h, wd = dy_nchw_f32.shape
+        if wt.dim() != 3 or wt.shape[1:] != (9, 8) or dx.shape != (b, h, wd, wt.shape[0]) or not (
+                dy_nchw_f32.is_contiguous() and wt.is_contiguous() and dx.is_contiguous()):
+            raise ValueError(f"dgrad_cout4: dy {tuple(dy_nchw_f32.shape)} takes contiguous wt [C,9,8] and dx [B,H,W,C], got "
+                             f"{tuple(wt.shape)} and {tuple(dx.shape)}")
+        self.conv_in_nchw(dy_nchw_f32, wt, None, dx)
+
+    def end_wgrad_splitm(self, m, cw):
+        """Default number of reduction slices of ``end_wgrad``: the output has only Cw/64 tiles (64 wide channels by all
+        36 thin columns) and a reduction of M = B*H*W pixels behind each; split it until the launch has about 2 workgroups
+        per CU, every slice keeping at least 64 pixels (the kernel itself takes slices down to one 32-pixel MFMA step,
+        ``splitm <= ceil(M/32)``): ``max(1, min(ceil(2 * CUs / (Cw/64)), ceil(M/64)))``, the rule of ``wgrad_splitm``."""
+        if self._n_cu is None:
+            self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        tiles = max(1, cw // 64)
+        return max(1, min(-(-2 * self._n_cu // tiles), -(-m // 64)))
+
+    def end_wgrad_partial_numel(self, splitm, ct, cw, mode):
+        """fp32 elements of the ``partial`` scratch of an ``end_wgrad`` call (nothing for ``splitm == 1``): per slice dw
+        in its final layout and the bias sums."""
+        n = int(self.lib.dadd_end_wgrad_partial_floats(int(mode), int(ct), int(cw), int(splitm)))
+        if n < 0:
+            raise ValueError(f"end_wgrad takes mode 0 or 1, Ct in 1..4 and Cw a multiple of 64 (got mode {mode}, Ct {ct}, Cw {cw})")
+        return n
+
+    def end_wgrad(self, thin, wide, dw, *, dbias=None, mode, splitm=None, partial=None):
+        """Weight (and bias) gradient of a 4-channel end conv (3x3, stride 1, padding 1), fp32, overwritten.  ``thin`` is
+        the fp32 NCHW tensor [B,Ct<=4,H,W], ``wide`` the fp16 or bf16 NHWC tensor [B,H,W,Cw] (possibly a channel slice of a
+        wider one: the row stride travels); thin is rounded to wide's type before the product, as the forward kernels do.
+        ``mode = lib.END_WGRAD_IN`` (conv_in: thin = latents, wide = dy): dw [Cw,9,8] in the ``pack_conv_cin8`` layout,
+        channels >= Ct written as zero, dbias [Cw] = column sums of wide.
+        ``mode = lib.END_WGRAD_OUT`` (conv_out: thin = dy, wide = x): dw [Ct,9,Cw] in the ``pack_conv_cout4`` layout,
+        dbias [Ct] = sums of the rounded thin planes.
+        ``splitm`` = number of slices of the pixel reduction; ``None`` takes ``end_wgrad_splitm``.  ``splitm > 1`` needs
+        ``partial``, fp32 with ``end_wgrad_partial_numel`` elements; the slabs are added in slice order by a second launch
+        of the same call, so the result is bit-reproducible."""
+        if thin.dim() != 4 or wide.dim() != 4 or thin.dtype != torch.float32 or not thin.is_contiguous():
+            raise ValueError(f"end_wgrad takes thin fp32 NCHW (contiguous) and wide NHWC, got {tuple(thin.shape)} {thin.dtype} "
+                             f"and {tuple(wide.shape)}")
+        b, ct, h, wd = thin.shape
+        cw = wide.shape[-1]
+        if wide.shape != (b, h, wd, cw):
+            raise ValueError(f"end_wgrad: thin {tuple(thin.shape)} and wide {tuple(wide.shape)} are not one map")
+        fn = getattr(self.lib, "dadd_conv_end_wgrad_" + _sfx(wide))
+        nb = cw if mode == L.END_WGRAD_IN else ct
+        want = (cw, 9, 8) if mode == L.END_WGRAD_IN else (ct, 9, cw)
+        if dw.dtype != torch.float32 or not dw.is_contiguous() or (mode in (L.END_WGRAD_IN, L.END_WGRAD_OUT)
+                                                                   and dw.numel() != want[0] * want[1] * want[2]):
+            raise ValueError(f"end_wgrad: dw must be contiguous fp32 {want}, got {tuple(dw.shape)} {dw.dtype}")
+        if dbias is not None and (dbias.dtype != torch.float32 or not dbias.is_contiguous() or dbias.numel() != nb):
+            raise ValueError(f"end_wgrad: dbias must be contiguous fp32 [{nb}], got {tuple(dbias.shape)} {dbias.dtype}")
+        if splitm is None:
+            splitm = self.end_wgrad_splitm(b * h * wd, cw)
+        if splitm > 1 and partial is not None:      # (a missing partial is the library's to refuse)
+            need = self.end_wgrad_partial_numel(splitm, ct, cw, mode)
+            if partial.dtype != torch.float32 or not partial.is_contiguous() or partial.numel() < need:
+                raise ValueError(f"end_wgrad: partial must be contiguous fp32 with at least {need} elements, got "
+                                 f"{tuple(partial.shape)} {partial.dtype}")
+        d = self._edesc
+        d.thin, d.wide, d.dw, d.dbias, d.partial = _p(thin), _p(wide), _p(dw), _p(dbias), _p(partial)
+        d.B, d.H, d.W, d.Ct, d.Cw = b, h, wd, ct, cw
+        d.ld_wide, d.mode, d.splitm = self._pixel_ld(wide), int(mode), int(splitm)
+        L.check(fn(C.byref(d), self.s))
+
+    def mse_rows_grad(self, pred, target, rowgrad, out):
+        """Backward of ``mse_rows``: out[b] = rowgrad[b] * (2 / per_sample) * (pred[b] - target[b]), all fp32; ``rowgrad``
+        [B] is the gradient of the B row means and is read on the device."""
+        b = pred.shape[0]
+        for t in (pred, target, rowgrad, out):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"mse_rows_grad takes contiguous fp32 tensors, got {tuple(t.shape)} {t.dtype}")
+        if pred.shape != target.shape or out.shape != pred.shape or rowgrad.numel() != b:
+            raise ValueError(f"mse_rows_grad: pred {tuple(pred.shape)}, target {tuple(target.shape)}, out {tuple(out.shape)} "
+                             f"and rowgrad {tuple(rowgrad.shape)} do not belong together")
+        L.check(self.lib.dadd_mse_rows_grad_f32(_p(pred), _p(target), _p(rowgrad), _p(out), b, pred.numel() // b, self.s))
 
     def dgrad_resample(self, dy, wt, dx, *, stride=1, ups=0):
         """Data gradient of the stride-2 (``stride=2``) or upsampled (``ups=1``) 3x3 ``igemm``, exactly one of the two:

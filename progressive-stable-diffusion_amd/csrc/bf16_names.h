@@ -37,6 +37,9 @@
 #define attn_grad_dkv_kernel attn_grad_dkv_kernel_bf16
 #define attn_grad_dq_kernel attn_grad_dq_kernel_bf16
 #define dgrad_kernel dgrad_kernel_bf16
+#define EndWgradArgs EndWgradArgs_bf16
+#define end_wgrad_kernel end_wgrad_kernel_bf16
+#define end_wgrad_finish_kernel end_wgrad_finish_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -76,3 +79,6 @@
 
 // C entry points (include/dadd_hip_dgrad.h)
 #define dadd_conv_dgrad_f16 dadd_conv_dgrad_bf16
+
+// C entry points (include/dadd_hip_end_grad.h)
+#define dadd_conv_end_wgrad_f16 dadd_conv_end_wgrad_bf16

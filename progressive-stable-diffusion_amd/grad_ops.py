@@ -12,8 +12,13 @@ saved input.  Attention: forward is ``HipBackend.self_attn`` / ``attention`` / `
 of csrc/attn_grad.hip (``attn_grad``: row statistics recomputed from q, k, v and dy, then dK / dV, then dQ); the
 triple-pathway gradient is composed from it, one call per pathway with the gate or lambda as the scale of dy.
 With these a ResnetBlock2D and a full BasicTransformerBlock (attn1, attn2, feed-forward) are differentiable end to end.
-These are operators, not the training loop: still missing are the 4-channel end convolutions, the wiring into
-``training_step`` and attention head dims other than 40 / 80 / 160.  The
+The UNet's 4-channel ends and the loss: ``conv_in`` (fp32 NCHW latents -> 16-bit NHWC, ``HipBackend.conv_in_nchw``) and
+``conv_out`` (16-bit NHWC -> fp32 NCHW, ``HipBackend.conv_cout4``) get their weight and bias gradients from the thin
+M-reduction GEMM of ``HipBackend.end_wgrad`` (csrc/end_grad.hip); the data gradient of ``conv_out`` is the conv_in kernel
+on dy with the weight re-laid by ``dgrad_weight_cout4`` (``HipBackend.dgrad_cout4``); ``mse_rows`` is the row-mean squared
+error with ``HipBackend.mse_rows_grad`` behind it.  A gradient now reaches every kind of UNet parameter.
+These are operators, not the training loop: still missing are the wiring into ``training_step`` and attention head dims
+other than 40 / 80 / 160.  The
 optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
 arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
 in the arena's flat gradient buffer).
@@ -71,6 +76,18 @@ def dgrad_weight_ups(w16: torch.Tensor) -> torch.Tensor:
     rows = torch.stack([w[:, list(s)].sum(1) for s in UPS_TAP_SETS], 1)          # [n][e][kx][c]
     w4 = torch.stack([rows[:, :, list(s)].sum(2) for s in UPS_TAP_SETS], 2)      # [n][e][f][c]
     return w4.permute(3, 1, 2, 0).reshape(c, 16 * n).to(w16.dtype).contiguous()
+
+
+def dgrad_weight_cout4(w16: torch.Tensor) -> torch.Tensor:
+    """``[Co<=4][9*C] -> [C][9][8]`` with the taps flipped and the columns ``>= Co`` zero: wt[c][8-tap][o] = w[o][tap][c],
+    the ``pack_conv_cin8`` layout of the transposed conv.  ``HipBackend.conv_in_nchw`` run on the fp32 NCHW dy of
+    ``conv_out`` with this weight is conv_out's data gradient (``HipBackend.dgrad_cout4``).  A torch re-layout, like
+    ``dgrad_weight``."""
+    co, c = w16.shape[0], w16.shape[1] // 9
+    assert w16.dim() == 2 and w16.shape[1] == 9 * c and 1 <= co <= 4
+    wt = w16.new_zeros((c, 9, 8))
+    wt[:, :, :co] = w16.reshape(co, 9, c).flip(1).permute(2, 1, 0)
+    return wt
 
 
 def _forward(be, x, w, bias, taps, stride, ups):
@@ -178,6 +195,166 @@ def upsample2d(be, x, w, bias=None):
     if x.dim() != 4:
         raise ValueError(f"upsample2d takes NHWC x, got {tuple(x.shape)}")
     return _Product.apply(x, w, bias, be, 9, 1, True)
+
+
+def _end_wgrad(be, thin, wide, dw_shape, nb, mode, need_db):
+    """dw (in the kernel's layout) and dbias of an end conv on the backend stream, default split."""
+    b, ct, h, wd = thin.shape
+    cw = wide.shape[-1]
+    dw = be.empty(dw_shape, torch.float32)
+    db = be.empty((nb,), torch.float32) if need_db else None
+    splitm = be.end_wgrad_splitm(b * h * wd, cw)
+    partial = be.empty((be.end_wgrad_partial_numel(splitm, ct, cw, mode),), torch.float32) if splitm > 1 else None
+    be.end_wgrad(thin, wide, dw, dbias=db, mode=mode, splitm=splitm, partial=partial)
+    return dw, db
+
+
+class _ConvIn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, be, dtype):
+        if x.dim() != 4 or x.dtype != torch.float32 or not 1 <= x.shape[1] <= 4:
+            raise ValueError(f"conv_in takes fp32 NCHW x with 1..4 channels, got {tuple(x.shape)} {x.dtype}")
+        b, ct, h, wd = x.shape
+        n = w.shape[0]
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"conv_in writes fp16 or bf16, got {dtype}")
+        if w.dtype != torch.float32 or w.shape != (n, 9 * ct) or n % 8 or (
+                bias is not None and (bias.dtype != torch.float32 or bias.shape != (n,))):
+            raise ValueError(f"w must be the fp32 master [N][9*{ct}] with N a multiple of 8 and bias fp32 [N], got "
+                             f"{tuple(w.shape)} {w.dtype}")
+        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and n % 64:
+            raise ValueError(f"conv_in: the weight / bias gradient takes N a multiple of 64, got {n} (detach w and bias for a "
+                             "forward alone)")
+        x = x.contiguous()
+        w8 = torch.zeros((n, 9, 8), dtype=dtype, device=w.device)     # pack_conv_cin8 of the rounded master
+        w8[:, :, :ct] = w.detach().reshape(n, 9, ct).to(dtype)
+        bias = None if bias is None else bias.detach().contiguous()
+        be.wait_current()
+        y = be.empty((b, h, wd, n), dtype)
+        be.conv_in_nchw(x, w8, bias, y)
+        be.release_to_current()
+        ctx.save_for_backward(x)
+        ctx.be = be
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        be = ctx.be
+        _, need_dw, need_db = ctx.needs_input_grad[:3]
+        if not (need_dw or need_db):
+            return (None,) * 5
+        ct, n = x.shape[1], dy.shape[-1]
+        dy = dy.contiguous()
+        be.wait_current()
+        dw8, db = _end_wgrad(be, x, dy, (n, 9, 8), n, L.END_WGRAD_IN, need_db)
+        with be.ctx():
+            dw = dw8[:, :, :ct].reshape(n, 9 * ct)
+        be.release_to_current()
+        return None, dw if need_dw else None, db, None, None
+
+
+class _ConvOut(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, be):
+        _check16(x, "x")
+        if x.dim() != 4:
+            raise ValueError(f"conv_out takes NHWC x, got {tuple(x.shape)}")
+        b, h, wd, c = x.shape
+        co = w.shape[0]
+        if w.dtype != torch.float32 or w.shape != (co, 9 * c) or not 1 <= co <= 4 or (
+                bias is not None and (bias.dtype != torch.float32 or bias.shape != (co,))):
+            raise ValueError(f"w must be the fp32 master [Co <= 4][9*{c}] and bias fp32 [Co], got {tuple(w.shape)} {w.dtype}")
+        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and c % 64:
+            raise ValueError(f"conv_out: the weight / bias gradient takes C a multiple of 64, got {c} (detach w and bias for a "
+                             "forward and a data gradient alone)")
+        x = x.contiguous()
+        w16 = w.detach().to(x.dtype).contiguous()   # [Co][9*C] is pack_conv_cout4's [Co][9][C]
+        bias = None if bias is None else bias.detach().contiguous()
+        be.wait_current()
+        y = be.empty((b, co, h, wd), torch.float32)
+        be.conv_cout4(x, w16.view(co, 9, c), bias, y, mode=0)
+        be.release_to_current()
+        ctx.save_for_backward(x, w16)
+        ctx.be = be
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w16 = ctx.saved_tensors
+        be = ctx.be
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        if not (need_dx or need_dw or need_db):
+            return (None,) * 4
+        co, c = w16.shape[0], x.shape[-1]
+        dy = dy.float().contiguous()
+        wt = dgrad_weight_cout4(w16) if need_dx else None      # torch plumbing, current stream
+        be.wait_current()
+        dx = dw = db = None
+        if need_dx:
+            dx = be.empty(tuple(x.shape), x.dtype)
+            be.dgrad_cout4(dy, wt, dx)
+        if need_dw or need_db:
+            dw, db = _end_wgrad(be, dy, x, (co, 9, c), co, L.END_WGRAD_OUT, need_db)
+            dw = dw.view(co, 9 * c)
+        be.release_to_current()
+        return dx, dw if need_dw else None, db, None
+
+
+class _MseRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, be):
+        if pred.dtype != torch.float32 or target.dtype != torch.float32 or pred.shape != target.shape or pred.dim() < 2:
+            raise ValueError(f"mse_rows takes fp32 pred and target of one shape [B, ...], got {tuple(pred.shape)} {pred.dtype} "
+                             f"and {tuple(target.shape)} {target.dtype}")
+        pred, target = pred.contiguous(), target.contiguous()
+        be.wait_current()
+        out = be.empty((pred.shape[0],), torch.float32)
+        be.mse_rows(pred, target, out)
+        be.release_to_current()
+        ctx.save_for_backward(pred, target)
+        ctx.be = be
+        return out
+
+    @staticmethod
+    def backward(ctx, drow):
+        pred, target = ctx.saved_tensors
+        be = ctx.be
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        drow = drow.float().contiguous()
+        be.wait_current()
+        dpred = be.empty(tuple(pred.shape), torch.float32)
+        be.mse_rows_grad(pred, target, drow, dpred)
+        be.release_to_current()
+        return dpred, None, None
+
+
+def conv_in(be, x_nchw, w, bias=None, dtype=torch.float16):
+    """The UNet's conv_in: 3x3, padding 1, of the fp32 NCHW latents ``x_nchw`` [B, Ct <= 4, H, W] with the fp32 master
+    ``w`` [N][9*Ct] -> ``dtype`` (fp16 or bf16) NHWC [B,H,W,N]; the latents are rounded to ``dtype`` in registers
+    (``HipBackend.conv_in_nchw``).  Differentiable in w and bias (``HipBackend.end_wgrad``, IN mode; N a multiple of
+    64: with a trainable w or bias any other N is refused by the forward, N a multiple of 8 suffices without).  The latents are data: there is no gradient of ``x_nchw``."""
+    if x_nchw.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("conv_in has no data gradient: the latents are data; pass x_nchw.detach() to get the "
+                                  "weight and bias gradients")
+    return _ConvIn.apply(x_nchw, w, bias, be, dtype)
+
+
+def conv_out(be, x, w, bias=None):
+    """The UNet's conv_out: 3x3, padding 1, of 16-bit NHWC ``x`` [B,H,W,C] with the fp32 master ``w`` [Co <= 4][9*C] ->
+    fp32 NCHW [B,Co,H,W] (``HipBackend.conv_cout4``, mode 0).  Differentiable in x, w and bias: the incoming fp32
+    gradient is rounded to ``x.dtype`` in registers by both backward kernels (``HipBackend.dgrad_cout4`` on the weight of
+    ``dgrad_weight_cout4``; ``HipBackend.end_wgrad``, OUT mode; C a multiple of 64: with a trainable w or bias any other C is refused by the
+    forward)."""
+    return _ConvOut.apply(x, w, bias, be)
+
+
+def mse_rows(be, pred, target):
+    """mean((pred - target)^2) over every axis but the first: fp32 [B, ...] -> fp32 [B] (``HipBackend.mse_rows``);
+    differentiable in pred (``HipBackend.mse_rows_grad``): whatever weights the rows afterwards - a Min-SNR weight, the
+    mean over the batch, a loss scale - reaches the kernel as the upstream gradient of the B rows, on the device."""
+    return _MseRows.apply(pred, target, be)
 
 
 def _check16(x, what):

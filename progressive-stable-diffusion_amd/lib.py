@@ -25,6 +25,8 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            "attn_grad.hip", "attn_grad_bf16.hip",
            # training backward: the data gradient of the stride-2 and upsampled 3x3 convs and its bf16 twin
            "dgrad.hip", "dgrad_bf16.hip",
+           # training backward: weight / bias gradient of the 4-channel end convs and the loss gradient, and its bf16 twin
+           "end_grad.hip", "end_grad_bf16.hip",
            # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (one source, no bf16 twin)
            "optim.hip")
 
@@ -36,6 +38,7 @@ EPI_GNAPPLY, EPI_GNAPPLY_SILU = 32768, 65536
 TUNE_SHALLOW, TUNE_NODMA, TUNE_PERSIST = 16, 32, 64
 XATTN_SPLIT, XATTN_BASELINE = 0, 1
 DGRAD_STRIDE2, DGRAD_UPS = 0, 1
+END_WGRAD_IN, END_WGRAD_OUT = 0, 1
 GN_MAX_CHUNKS = 256
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -81,6 +84,12 @@ class DgradClass(C.Structure):
 class DgradChoice(C.Structure):
     """Mirror of ``dadd_dgrad_choice``: what ``dadd_conv_dgrad_*`` would launch for a descriptor."""
     _fields_ = [(n, i32) for n in ("grid_x", "grid_y", "block", "smem", "nclass", "xcd_by_c")] + [("cls", DgradClass * 4)]
+
+
+class EndWgradDesc(C.Structure):
+    """Mirror of ``dadd_end_wgrad_desc``."""
+    _fields_ = [(n, vp) for n in ("thin", "wide", "dw", "dbias", "partial")] + \
+               [(n, i32) for n in ("B", "H", "W", "Ct", "Cw", "ld_wide", "mode", "splitm")]
 
 
 class GnGradDesc(C.Structure):
@@ -202,6 +211,14 @@ DGRAD_PROTOTYPES = {
     "dadd_conv_dgrad_resolve": (C.c_int, [C.POINTER(DgradDesc), C.POINTER(DgradChoice)]),
 }
 
+# every symbol include/dadd_hip_end_grad.h declares (gradients of the 4-channel end convs and of the loss, csrc/end_grad.hip)
+END_GRAD_PROTOTYPES = {
+    "dadd_conv_end_wgrad_f16": (C.c_int, [C.POINTER(EndWgradDesc), vp]),
+    "dadd_conv_end_wgrad_bf16": (C.c_int, [C.POINTER(EndWgradDesc), vp]),
+    "dadd_end_wgrad_partial_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dadd_mse_rows_grad_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, i64, vp]),
+}
+
 # include/dadd_hip_optim.h: the optimizer step (csrc/optim.hip)
 OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8
 OPTIM_EMA, OPTIM_P16_F16, OPTIM_P16_BF16, OPTIM_ZERO_GRAD = 1, 2, 4, 8
@@ -238,7 +255,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
         [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
-                                                                       "dadd_hip_attn_grad.h", "dadd_hip_optim.h", "dadd_hip_dgrad.h")]
+                                                                       "dadd_hip_attn_grad.h", "dadd_hip_optim.h", "dadd_hip_dgrad.h",
+                                                                       "dadd_hip_end_grad.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -265,7 +283,7 @@ def load() -> C.CDLL:
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
-                              **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES}.items():
+                              **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES, **END_GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
