@@ -690,6 +690,11 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
   out->tile_n = tile_n;
   out->persistent = !halo && persistent;
   out->grid = out->persistent ? dim3(num_cu) : dim3(a.mtiles * a.ntiles, out->nsplit);
+  // Run-ahead weight prefetch of igemm_dma.hip (igemm_args.h): the first DADD_PF_KTILES weight tiles of a K slice, where
+  // at least DADD_PF_MIN_SHARE row-tile workgroups share the strip and split its lines between them.  Not on the
+  // persistent ring, whose workgroups walk runs of tiles, and not on the halo conv (measured: no gain there).
+  a.pf_kt = (dma && !halo && a.korder == 0 && !out->persistent && a.mtiles >= DADD_PF_MIN_SHARE)
+                ? (a.kps < DADD_PF_KTILES ? a.kps : DADD_PF_KTILES) : 0;
   if (halo) {
     DADD_REQUIRE(window, "conv_halo: operand larger than the 2 GiB buffer window");
     const bool duo = (d->flags & DADD_TUNE_SHALLOW) != 0 && !(a.flags & DADD_PRE_GN);   // A/B: the two-MFMA-waves-per-SIMD build

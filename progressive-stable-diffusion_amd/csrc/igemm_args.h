@@ -45,7 +45,48 @@ struct IgemmArgs {
   dadd_fastdiv fd_howo, fd_wo, fd_cin;   // row -> (sample, y, x); K offset -> tap
   dadd_fastdiv fd_t0, fd_t1, fd_t2;      // tile_decode: tiles per group (or ntiles), row tiles per group, column groups
   int ngn;                               // ntiles / gn (2-D groups)
+  int pf_kt;                             // run-ahead weight prefetch (below): K tiles of a slice that are prefetched, 0 = none
 };
+
+// ---- run-ahead prefetch of the weight strip (igemm_dma.hip) -------------------------------------------------------
+// The weights are cold at every launch of a step.  All p.mtiles row-tile workgroups of one column
+// tile and K slice stream the SAME weight strip, each through a ring with three K tiles in flight, so the whole chip has
+// only those three tiles of a strip on their way from HBM.  The MFMA waves, idle until the first K tiles have landed,
+// therefore touch the first pf_kt K tiles of the strip ahead of the rings — one dword per 128-byte line, the lines
+// dealt round-robin over the sharing workgroups (workgroup mt takes lines mt, mt + mtiles, ...), so every line is
+// requested once and a workgroup issues a handful of loads.  (Every workgroup touching its WHOLE strip was measured
+// first and is slower than no prefetch, hot and cold: 2,000 single-line requests per workgroup queue in the CU's one
+// vector-memory pipe ahead of the ring DMA, profiles/r11_*.  The halo conv and strips shared by only eight workgroups
+// measured no gain in the shared form and have none.)  The descriptor has the base and num_records of the DMA's;
+// rows past N and lines past the slice get an out-of-range offset and move nothing.  The loads are never consumed.
+// They all name ONE destination register that the caller keeps alive until dadd_pf_drain — an s_waitcnt vmcnt(0) in
+// front of the epilogue, where they are long complete — because the compiler does not know that a load is outstanding
+// on an inline-asm result and would hand the register to the main loop otherwise.  Only the MFMA waves may issue them:
+// the loader waves' counted vmcnt waits assume that nothing but their ring DMA is in flight.
+// DADD_PF_KTILES: how far ahead, in K tiles of a launch slice (0 = no prefetch); DADD_PF_MIN_SHARE: fewest workgroups
+// per strip for which dadd_igemm_resolve turns it on.  The macros exist for the sweep builds; the product library is
+// built without them.
+#ifndef DADD_PF_KTILES
+#define DADD_PF_KTILES 24
+#endif
+#ifndef DADD_PF_MIN_SHARE
+#define DADD_PF_MIN_SHARE 16
+#endif
+typedef unsigned dadd_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ dadd_u4 dadd_pf_desc(const void* base, int bytes) {
+  const unsigned long long a = (unsigned long long)base;
+  return dadd_u4{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, (unsigned)bytes, 0x00020000u};
+}
+__device__ __forceinline__ void dadd_pf_line(unsigned& sink, unsigned off, dadd_u4 desc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "+v"(sink) : "v"(off), "s"(desc));
+#endif
+}
+__device__ __forceinline__ void dadd_pf_drain(unsigned& sink) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(sink)::"memory");
+#endif
+}
 
 // output row -> sample (rowvec / GroupNorm-statistics addressing) and -> (sample, y, x) (the im2col gather)
 __device__ __forceinline__ int row_sample(const IgemmArgs& p, int m, int HoWo) {

@@ -337,6 +337,26 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
     fa[s2] = lds_off(wm * WM + (lane & 15), s2 * 4 + fq) * 2;
     fb[s2] = A_BYTES + lds_off(wn * WN + (lane & 15), s2 * 4 + fq) * 2;
   }
+  // Run-ahead prefetch of the weight strip (igemm_args.h): rows n0 .. n0+BN, the first p.pf_kt K tiles of the slice, K
+  // tile outer / row inner.  The strip is shared by the p.mtiles row-tile workgroups of this column tile and K slice:
+  // workgroup mt takes lines mt, mt + mtiles, ...  These waves would otherwise sit at the barrier below; they issue no
+  // other vector memory operation before the epilogue.  (Never with PERS: dadd_igemm_resolve.)
+  unsigned pf_sink = 0;
+  if (!PERS && p.pf_kt > 0) {
+    int nt, mt;
+    tile_decode_fast(p, tile_first, mt, nt);
+    mt = __builtin_amdgcn_readfirstlane(mt);
+    const int n0 = __builtin_amdgcn_readfirstlane(nt) * BN;
+    const dadd_u4 dw = dadd_pf_desc(p.w, recW);
+    const unsigned row_bytes = (unsigned)p.K * 2u;
+    const int total = BN * min(nk, p.pf_kt);
+    for (int q0 = wave * 64; q0 * p.mtiles + mt < total; q0 += 256) {   // wave-uniform bound
+      const int l = (q0 + lane) * p.mtiles + mt;
+      const int kt = l / BN, n = n0 + l - kt * BN;
+      const unsigned off = (l < total && n < p.N) ? (unsigned)n * row_bytes + (unsigned)((kt0 + kt) * BK * 2) : OOB;
+      dadd_pf_line(pf_sink, off, dw);
+    }
+  }
   __builtin_amdgcn_s_barrier();   // tiles 0 and 1 landed
   __builtin_amdgcn_sched_barrier(0);
   h8 xa0[MI], wb0[J], xa1[MI], wb1[J];
@@ -400,6 +420,7 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
       comp_off = next_off;
       __builtin_amdgcn_sched_barrier(0);
     }
+    dadd_pf_drain(pf_sink);   // the prefetch loads are long complete; their register is free from here on
     int nt, mt;
     tile_decode_fast(p, tile_first + tl, mt, nt);
     if constexpr (LNF) {
