@@ -385,7 +385,7 @@ __global__ __launch_bounds__(DUO ? 768 : 512, 1) void conv3x3_halo_kernel(const 
     for (int j = 0; j < J; ++j)
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[j][i] += park[(j * 4 + i) * 64 + lane];
-    igemm_epilogue<J, 4, 64, WN>(p, acc, m0, n0, wm, wn, lane, z, smem, nullptr, nullptr, smem + GN_OFF);
+    igemm_epilogue<J, 4, 64, WN, EPI_COLS>(p, acc, m0, n0, wm, wn, lane, z, smem, nullptr, nullptr, smem + GN_OFF);   // 768 threads: 168 registers
     return;
   }
   if constexpr (GNIN) {

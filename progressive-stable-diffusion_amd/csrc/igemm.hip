@@ -36,6 +36,9 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs p) {
   constexpr int MI = WM / 16;      // m-fragments per wave (4 or 2)
   constexpr int WN = BN / 2;       // columns per wave
   constexpr int J = WN / 16;       // n-fragments per wave (4 or 5)
+  // operand batches of the epilogue (igemm_epilogue.h): the two-tiles-in-flight pipeline at BN = 128 has no registers to
+  // spare without giving up a wave per SIMD (64 rows) or spilling (128 rows)
+  constexpr int EPI = (DEEP && BN == 128) ? EPI_COLS : EPI_TILE;
   constexpr int NA = BM * 8 / 256; // 16-byte activation loads per thread per K tile
   constexpr int NB = BN * 8 / 256; // 16-byte weight loads per thread per K tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -193,7 +196,10 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-  igemm_epilogue<J, MI, WM, WN>(p, acc, m0, n0, wm, wn, lane, z, smem, nullptr, nullptr, ln_scr, ln_sts ? ln_scr + LN_LDS_STATS : nullptr,
+  // (the lane id taken afresh: the epilogue's lane-derived addresses then are not computed ahead of the K loop and
+  // carried, or spilled, across it)
+  const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  igemm_epilogue<J, MI, WM, WN, EPI>(p, acc, m0, n0, wm, wn, lane_e, z, smem, nullptr, nullptr, ln_scr, ln_sts ? ln_scr + LN_LDS_STATS : nullptr,
                                 ln_stage ? ln_scr : nullptr);
 }
 

@@ -53,6 +53,8 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
   constexpr int WM = BM / 2, MI = WM / 16;   // compute waves: 2 (M) x 2 (N); rows / 16-row fragments per wave
   constexpr int WN = BN / 2;
   constexpr int J = WN / 16;
+  // operand batches of the epilogue (igemm_epilogue.h): the persistent ring keeps the next tile's fragments live across it
+  constexpr int EPI = !PERS ? EPI_TILE : (BN == 160 && LNK == 2) ? EPI_COLS : EPI_ROWS;
   constexpr int NA = BM / 32;   // DMA instructions per loader wave per tile, activations (2 or 4)
   constexpr int NBJ = BN / 32;  // DMA instructions per wave per tile, weights (4 or 5)
   constexpr int LPT = NA + NBJ;
@@ -425,9 +427,9 @@ __global__ __launch_bounds__(512, (BM + BN) <= 128 ? 4 : 2) void igemm_dma_kerne
     tile_decode_fast(p, tile_first + tl, mt, nt);
     if constexpr (LNF) {
       ln_finish<MI>(ls1, ls2, p.K, p.ln_eps);
-      igemm_epilogue<J, MI, WM, WN>(p, acc, mt * BM, nt * BN, wm, wn, lane, z, smem, ls1, ls2);
+      igemm_epilogue<J, MI, WM, WN, EPI>(p, acc, mt * BM, nt * BN, wm, wn, lane, z, smem, ls1, ls2);
     } else {
-      igemm_epilogue<J, MI, WM, WN>(p, acc, mt * BM, nt * BN, wm, wn, lane, z, smem, nullptr, nullptr, smem + 4 * STAGE,
+      igemm_epilogue<J, MI, WM, WN, EPI>(p, acc, mt * BM, nt * BN, wm, wn, lane, z, smem, nullptr, nullptr, smem + 4 * STAGE,
                                     ln_sts ? ln_scr + LN_LDS_STATS : nullptr, ln_stage ? ln_scr : nullptr);
     }
   }
