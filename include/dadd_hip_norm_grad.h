@@ -35,15 +35,15 @@ typedef struct dadd_gn_grad_desc {
 /* Backward of dadd_groupnorm_* (y = [silu](xhat * gamma + beta), xhat = (x - mean_bg) * rstd_bg over the HW * C/groups
  * values of a (sample, group)): dx = rstd * (dz * gamma - (s1 + xhat * s2) / n) with dz = dy [* silu'(z)],
  * s1 = sum dz * gamma, s2 = sum dz * gamma * xhat over the (sample, group); dgamma[c] = sum_{b,hw} dz * xhat,
- * dbeta[c] = sum_{b,hw} dz.  Mean and rstd are recomputed from x (fp32 chunk sums combined in double, max(var, 0)),
- * the forward saves nothing.  Contract as the forward: C1 > 0, C1 and C2 multiples of 8, groups <= 32 dividing C,
+ * dbeta[c] = sum_{b,hw} dz.  Mean and rstd are recomputed from x (fp32 chunk sums of x - p and (x - p)^2 about the slab's
+ * first element p, combined in double, max(var, 0): accurate however far from zero the group sits), the forward saves nothing.  Contract as the forward: C1 > 0, C1 and C2 multiples of 8, groups <= 32 dividing C,
  * C <= 4096, x1 / x2 / dy / dx1 / dx2 16-byte aligned, at least one output.  Replaces torch's native_group_norm_backward
  * (+ silu_backward, + the split of the concat gradient) in a training step. */
 int dadd_groupnorm_grad_f16(const dadd_gn_grad_desc* d, void* stream);
 int dadd_groupnorm_grad_bf16(const dadd_gn_grad_desc* d, void* stream);
 
 /* Host only: the number of floats of `ws` for a dadd_groupnorm_grad_* call of these sizes (either 16-bit type), or -1
- * when the sizes break the contract above.  Layout: [B][nchunk][groups][2] sums of x and x^2, [B][nchunk][groups][2]
+ * when the sizes break the contract above.  Layout: [B][nchunk][groups][2] sums of x - p and (x - p)^2, [B][nchunk][groups][2]
  * sums of dz * gamma and dz * gamma * xhat, [B][nchunk][C][2] sums of dz and dz * xhat; nchunk <= 64 row chunks. */
 long long dadd_groupnorm_grad_ws_floats(int B, int HW, int C, int groups);
 

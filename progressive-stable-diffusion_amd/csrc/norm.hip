@@ -6,6 +6,7 @@
 namespace {
 
 constexpr int GN_MAXV = 2;  // 16-byte channel vectors per thread: C <= 8*256*2 = 4096
+constexpr float GN_FAR = 256.f;  // |shift| above which gn_apply_kernel subtracts the mean before it scales
 
 struct GnArgs {
   const half_t* x1;
@@ -164,6 +165,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs p) {
   const int row0 = blockIdx.x * p.rows_per_block;
   const int row1 = min(p.HW, row0 + p.rows_per_block);
   float sc[GN_MAXV][8], sh[GN_MAXV][8];     // this thread's channels are the same for every row
+  bool far = false;
 #pragma unroll
   for (int u = 0; u < GN_MAXV; ++u) {
     const int v = tv + u * p.TV;
@@ -171,7 +173,35 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnArgs p) {
     for (int e = 0; e < 8; ++e) {
       sc[u][e] = v < nvec ? scale[v * 8 + e] : 0.f;
       sh[u][e] = v < nvec ? shift[v * 8 + e] : 0.f;
+      far |= fabsf(sh[u][e]) > GN_FAR;
     }
+  }
+  if (far) {
+    // One of this thread's channels has |shift| = |beta - mean * rstd * gamma| above GN_FAR: a group that is nearly
+    // constant far from zero (rstd -> eps^-1/2).  x * scale + shift then cancels two numbers of that size and keeps the
+    // fp32 rounding of the shift, |shift| * 2^-24 (64 * 1000 * 2^-24 = 4e-3 for a group constant at 64 with eps = 1e-6),
+    // so the mean is subtracted from x first: exact for a 16-bit x near the mean.  One row at a time, the operands from
+    // LDS / L2: this path is rare.  At the threshold the shift form is still good to 256 * 2^-24 = 1.5e-5, a hundredth
+    // of the 16-bit tolerance, so nothing jumps where the forms change.
+    for (int row = row0 + tr; row < row1; row += p.RP) {
+      const size_t pix = (size_t)b * p.HW + row;
+#pragma unroll 1
+      for (int u = 0; u < GN_MAXV; ++u) {
+        const int v = tv + u * p.TV;
+        if (v >= nvec) continue;
+        const h8 xv = gn_load(p, pix, v * 8);
+        h8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int c = v * 8 + e;
+          float f = ((float)xv[e] - st[2 * (c / p.cg)]) * scale[c] + p.beta[c];
+          if (p.silu) f = dadd_silu(f);
+          o[e] = (half_t)f;
+        }
+        *reinterpret_cast<h8*>(p.out + pix * p.C + v * 8) = o;
+      }
+    }
+    return;
   }
   for (int row = row0 + tr; row < row1; row += 4 * p.RP) {   // four rows in flight per thread
     h8 xv[4][GN_MAXV];

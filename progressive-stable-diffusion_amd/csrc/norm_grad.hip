@@ -17,7 +17,7 @@ struct GnGradArgs {
   const float* beta;
   half_t* dx1;
   half_t* dx2;
-  float* st;   // [B][nchunk][groups][2] sum x, sum x^2
+  float* st;   // [B][nchunk][groups][2] sum (x - p), sum (x - p)^2 about the group's pivot p
   float* gp;   // [B][nchunk][groups][2] sum dz*gamma, sum dz*gamma*xhat
   float* cp;   // [B][nchunk][C][2]      sum dz, sum dz*xhat
   int C1, C2, C, HW, groups, cg, nchunk, rows_per_chunk, rows_per_block, TV, RP, silu;
@@ -78,6 +78,16 @@ __device__ __forceinline__ void gng_combine(const float* part, int nchunk, int g
   }
 }
 
+// The statistics are summed ABOUT A PIVOT, the first element of the (sample, group) slab: sum (x - p) and sum (x - p)^2.
+// E[(x-p)^2] - E[x-p]^2 cancels numbers of the size of the spread, not of the mean, so rstd keeps its accuracy when a
+// group sits far from zero.  dgamma needs that: its bound (M + 16) 2^-24 sum |dz xhat| asks about 1e-6 of rstd, which
+// plain sums of x and x^2 lose at |mean| = 32 sigma (the forward's 16-bit outputs do not notice 1e-4 of rstd).
+__device__ __forceinline__ float gng_pivot(const GnGradArgs& p, int b, int g) {
+  const int c = g * p.cg;
+  const size_t pix = (size_t)b * p.HW;
+  return (float)((c < p.C1) ? p.x1[pix * p.C1 + c] : p.x2[pix * p.C2 + (c - p.C1)]);
+}
+
 // mean and rstd of every group of sample b -> lst[2g], lst[2g + 1] (the caller synchronises)
 __device__ __forceinline__ void gng_mean_rstd(const GnGradArgs& p, int b, int t, float* lst) {
   double a, q;
@@ -85,15 +95,16 @@ __device__ __forceinline__ void gng_mean_rstd(const GnGradArgs& p, int b, int t,
   const int g = t >> 3;
   if (g < p.groups && (t & 7) == 0) {
     const double n = (double)p.HW * (double)p.cg;
-    const double mu = a / n;
-    double var = q / n - mu * mu;
+    const double d = a / n;                    // mean - pivot
+    double var = q / n - d * d;
     if (var < 0.0) var = 0.0;
-    lst[2 * g] = (float)mu;
+    lst[2 * g] = (float)((double)gng_pivot(p, b, g) + d);
     lst[2 * g + 1] = (float)(1.0 / sqrt(var + (double)p.eps));
   }
 }
 
-// pass 1: per (sample, row chunk) sums of x and x^2 per group - the sums of gn_stats_kernel.  grid (nchunk, B)
+// pass 1: per (sample, row chunk) sums of x - p and (x - p)^2 per group, p the group's pivot (gng_pivot); otherwise the
+// sums of gn_stats_kernel.  grid (nchunk, B)
 template <int NV>
 __global__ __launch_bounds__(256) void gn_grad_stats_kernel(const GnGradArgs p) {
   extern __shared__ float sm[];  // [RP][C] sums, [RP][C] squares
@@ -102,11 +113,15 @@ __global__ __launch_bounds__(256) void gn_grad_stats_kernel(const GnGradArgs p) 
   const int row0 = chunk * p.rows_per_chunk;
   const int row1 = min(p.HW, row0 + p.rows_per_chunk);
   const int nvec = p.C >> 3;
-  float s[NV][8], ss[NV][8];
+  float s[NV][8], ss[NV][8], pv[NV][8];
 #pragma unroll
   for (int u = 0; u < NV; ++u)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[u][e] = ss[u][e] = 0.f;
+    for (int e = 0; e < 8; ++e) {
+      s[u][e] = ss[u][e] = 0.f;
+      const int v = tv + u * p.TV;
+      pv[u][e] = (tr < p.RP && v < nvec) ? gng_pivot(p, b, (v * 8 + e) / p.cg) : 0.f;
+    }
   if (tr < p.RP) {
     for (int row = row0 + tr; row < row1; row += 4 * p.RP) {   // four rows in flight per thread
       h8 xv[4][NV];
@@ -128,7 +143,7 @@ __global__ __launch_bounds__(256) void gn_grad_stats_kernel(const GnGradArgs p) 
           if (tv + u * p.TV < nvec) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const float f = (float)xv[q][u][e];
+              const float f = (float)xv[q][u][e] - pv[u][e];
               s[u][e] += f;
               ss[u][e] += f * f;
             }

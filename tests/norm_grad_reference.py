@@ -177,8 +177,8 @@ def gn_geometry(b, hw, c):
 
 
 def gn_model(x16, dy16, gamma, beta, eps, silu, groups=GROUPS):
-    """-> dx (x16.dtype), dgamma, dbeta (fp32) by the passes of the kernels: fp32 chunk sums of x and x^2 combined in double
-    with max(var, 0); per-chunk channel sums of dz and dz*xhat, their gamma-weighted group sums combined in double into
+    """-> dx (x16.dtype), dgamma, dbeta (fp32) by the passes of the kernels: fp32 chunk sums of x - p and (x - p)^2 about
+    the slab's first element p, combined in double with max(var, 0); per-chunk channel sums of dz and dz*xhat, their gamma-weighted group sums combined in double into
     s1/n and s2/n; dx = rstd * (dz*gamma - (s1/n + xhat * s2/n)); the channel sums added over (sample, chunk) in double."""
     b, h, w, c = x16.shape
     hw, cg = h * w, c // groups
@@ -186,11 +186,14 @@ def gn_model(x16, dy16, gamma, beta, eps, silu, groups=GROUPS):
     x, dy = x16.float().reshape(b, hw, c), dy16.float().reshape(b, hw, c)
     chunks = [slice(k * rows, min(hw, (k + 1) * rows)) for k in range(nchunk)]
     n = float(hw * cg)
-    st = torch.stack([torch.stack([x[:, s].reshape(b, -1, groups, cg).sum(dim=(1, 3)),
-                                   (x[:, s] ** 2).reshape(b, -1, groups, cg).sum(dim=(1, 3))], -1) for s in chunks], 1)
+    piv = x[:, 0].reshape(b, groups, cg)[:, :, 0]                    # [B][G]: the first element of every slab
+    xp = x - piv.repeat_interleave(cg, dim=1)[:, None, :]
+    st = torch.stack([torch.stack([xp[:, s].reshape(b, -1, groups, cg).sum(dim=(1, 3)),
+                                   (xp[:, s] ** 2).reshape(b, -1, groups, cg).sum(dim=(1, 3))], -1) for s in chunks], 1)
     tot = st.double().sum(dim=1)                                     # [B][G][2]
-    mu = tot[..., 0] / n
-    var = (tot[..., 1] / n - mu * mu).clamp_min(0.0)
+    d = tot[..., 0] / n
+    var = (tot[..., 1] / n - d * d).clamp_min(0.0)
+    mu = piv.double() + d
     mean = mu.float().repeat_interleave(cg, dim=1)[:, None, :]       # [B][1][C]
     rstd = (1.0 / torch.sqrt(var + eps)).float().repeat_interleave(cg, dim=1)[:, None, :]
     xhat = (x - mean) * rstd
