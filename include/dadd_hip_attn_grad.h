@@ -45,10 +45,11 @@ typedef struct dadd_attn_grad_desc {
  * rounded to the storage type as the operand of P^T dO; dS is computed from the fp32 P, dP and D and rounded to the
  * storage type as the operand of dS^T Q and dS K.  LSE, D, the scale of dout and every accumulator are fp32; each
  * output is rounded once when it is stored.
- * Contract: d in {40, 80, 160}; Nq and Nk multiples of 16, at least 16; every ld_* a multiple of 8 and at least
- * heads * d; every bs_* a non-negative multiple of 8; all tensor pointers 16-byte aligned; ws non-NULL (8-byte
- * aligned); at least one output.  Outputs must not alias inputs.  Columns outside the heads * d of a written row are
- * left untouched. */
+ * Contract: d in {40, 80, 96, 160}; Nq a multiple of 16, at least 16; Nk any positive count (keys past Nk are masked
+ * per key in all three kernels and their rows are neither read nor written; csrc/attn_grad.hip argues every key
+ * index); every ld_* a multiple of 8 and at least heads * d; every bs_* a non-negative multiple of 8; all tensor
+ * pointers 16-byte aligned; ws non-NULL (8-byte aligned); at least one output.  Outputs must not alias inputs.
+ * Columns outside the heads * d of a written row are left untouched. */
 int dadd_attn_grad_f16(const dadd_attn_grad_desc* d, void* stream);
 int dadd_attn_grad_bf16(const dadd_attn_grad_desc* d, void* stream);
 

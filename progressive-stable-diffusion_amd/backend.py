@@ -549,6 +549,75 @@ class HipBackend:
         assert h.is_contiguous() and dy.is_contiguous() and dh.is_contiguous()
         L.check(fn(_p(h), _p(dy), _p(dh), h.numel() // (2 * f), f, self.s))
 
+    # -- training kernels of the conditioning front-end (csrc/cond_grad.hip)
+    def gelu(self, x, y):
+        """Exact-form GELU as a layer of its own: y = gelu(x) over x [..., F], fp16 or bf16, the value the EPI_GELU
+        epilogue stores for the same rounded input.  The training step keeps x for ``gelu_grad``; the inference modules
+        keep the GEMM epilogue."""
+        f = x.shape[-1]
+        fn = getattr(self.lib, "dadd_gelu_" + _sfx(x, y))
+        if f % 8 or f == 0:
+            raise ValueError(f"gelu: F = {f} must be a positive multiple of 8")
+        assert y.shape == x.shape and x.is_contiguous() and y.is_contiguous() and x.dtype in _SFX
+        L.check(fn(_p(x), _p(y), x.numel() // f, f, self.s))
+
+    def gelu_grad(self, x, dy, dx):
+        """Backward of ``gelu``: dx = dy * (Phi(x) + x * phi(x)), Phi from the same erf approximation as the forward.
+        x, dy and dx [..., F], all fp16 or all bf16."""
+        f = x.shape[-1]
+        fn = getattr(self.lib, "dadd_gelu_grad_" + _sfx(x, dy, dx))
+        if f % 8 or f == 0:
+            raise ValueError(f"gelu_grad: F = {f} must be a positive multiple of 8")
+        assert dy.shape == x.shape and dx.shape == x.shape and x.dtype in _SFX
+        assert x.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
+        L.check(fn(_p(x), _p(dy), _p(dx), x.numel() // f, f, self.s))
+
+    def purifier_gate_tail(self, img, dis, z, gamma, beta, out, eps=1e-5):
+        """The FeaturePurifier's tail for training: out = LayerNorm(img - sigmoid(z) * dis) over the last axis.  img, dis
+        and z [..., C] fp16 or bf16, z the gate's pre-activation (``purifier_tail`` takes the gate itself); gamma, beta
+        fp32 [C]; out fp32 [..., C].  C a multiple of 8, at most 2048."""
+        c = img.shape[-1]
+        fn = getattr(self.lib, "dadd_purifier_gate_tail_" + _sfx(img, dis, z))
+        for t in (img, dis, z):
+            assert t.is_contiguous() and t.dtype in _SFX and t.shape == img.shape, "img, dis, z: one 16-bit shape"
+        assert out.dtype == torch.float32 and out.shape == img.shape and out.is_contiguous()
+        assert all(t.dtype == torch.float32 and t.numel() == c and t.is_contiguous() for t in (gamma, beta))
+        L.check(fn(_p(img), _p(dis), _p(z), _p(gamma), _p(beta), _p(out), img.numel() // max(c, 1), c, float(eps), self.s))
+
+    def purifier_gate_tail_grad_ws_numel(self, m, c):
+        """fp32 elements of the ``ws`` scratch of ``purifier_gate_tail_grad``: per-workgroup column sums [nblk][C][2]."""
+        n = int(self.lib.dadd_purifier_gate_tail_grad_ws_floats(m, c))
+        if n < 0:
+            raise ValueError(f"purifier_gate_tail_grad takes C a multiple of 8 up to 2048 and at least one row (got M {m}, C {c})")
+        return n
+
+    def purifier_gate_tail_grad(self, img, dis, z, dout, gamma, *, dimg=None, ddis=None, dz=None, dgamma=None, dbeta=None,
+                                ws=None, eps=1e-5):
+        """Backward of ``purifier_gate_tail``: from the forward's inputs img, dis, z [..., C] (fp16 or bf16) and the fp32
+        dout of the same shape, dimg / ddis / dz in the inputs' type and dgamma / dbeta [C] in fp32, overwritten.  The
+        gate, the row statistics and xhat are recomputed.  Each of ``dimg`` / ``ddis`` / ``dz`` may be None; ``dgamma`` and
+        ``dbeta`` are None together; at least one output.  The parameter gradients need ``ws``, fp32 scratch of
+        ``purifier_gate_tail_grad_ws_numel`` elements.  One launch over the rows and one for the column sums, fixed
+        summation order: bit-reproducible."""
+        c = img.shape[-1]
+        m = img.numel() // max(c, 1)
+        fn = getattr(self.lib, "dadd_purifier_gate_tail_grad_" + _sfx(img, dis, z, dimg, ddis, dz))
+        need = self.purifier_gate_tail_grad_ws_numel(m, c)
+        for t in (img, dis, z, dimg, ddis, dz):
+            assert t is None or (t.is_contiguous() and t.dtype in _SFX and t.shape == img.shape), "one 16-bit shape"
+        assert dout.dtype == torch.float32 and dout.shape == img.shape and dout.is_contiguous()
+        assert gamma.dtype == torch.float32 and gamma.numel() == c and gamma.is_contiguous()
+        if (dgamma is None) != (dbeta is None):
+            raise ValueError("purifier_gate_tail_grad: dgamma and dbeta come together")
+        if dimg is None and ddis is None and dz is None and dgamma is None:
+            raise ValueError("purifier_gate_tail_grad: no output")
+        if dgamma is not None:
+            assert dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c \
+                and dgamma.is_contiguous() and dbeta.is_contiguous()
+            assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        L.check(fn(_p(img), _p(dis), _p(z), _p(dout), _p(gamma), _p(dimg), _p(ddis), _p(dz), _p(dgamma), _p(dbeta), _p(ws),
+                   m, c, float(eps), self.s))
+
     # -- training backward of attention (csrc/attn_grad.hip)
     def attn_grad_ws_numel(self, b, heads, nq):
         """fp32 elements of the ``ws`` scratch of an ``attn_grad`` call: (LSE, D) per (sample, head, query row)."""
@@ -572,8 +641,8 @@ class HipBackend:
         dk, dv [B,Nk,C] (one row stride) of softmax(q k^T / sqrt(d)) v, for dout * do_scale * do_scale_dev[0]
         (``do_scale_dev``: device fp32[1], read by the kernels).  Each output may be None; without dk and dv the dkv launch
         is skipped, without dq the dq launch.  ``ws`` is fp32 scratch of ``attn_grad_ws_numel`` elements.  Up to three
-        launches (row statistics, dK / dV, dQ), fixed summation order: bit-reproducible.  d in {40, 80, 160}; Nq and Nk
-        multiples of 16."""
+        launches (row statistics, dK / dV, dQ), fixed summation order: bit-reproducible.  d in {40, 80, 96, 160}; Nq a
+        multiple of 16; Nk any positive count (257 CLIP tokens: the rows past Nk of a longer buffer are never touched)."""
         fn = getattr(self.lib, "dadd_attn_grad_" + _sfx(q, k, v, dout, dq, dk, dv))
         for t in (q, k, v, dout, dq, dk, dv):
             if t is not None and t.dtype not in _SFX:

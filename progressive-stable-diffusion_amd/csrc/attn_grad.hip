@@ -29,7 +29,30 @@
 // P = 0 in the dkv kernel and are never stored by the dq kernel; the running maximum starts at a large finite negative
 // and the first tile's rescale factor is exp2(-1e30 - m) = 0 against sums that are still 0: no inf, no 0 * inf.
 //
-// Resources per workgroup of 256 threads: LDS 2 tiles of 64 x (D + 8) halfs (18 / 26 / 42 KB for d = 40 / 80 / 160) plus
+//
+// Nk is any positive count (Nq stays a multiple of 16).  Every place a key index is formed, and why no multiple of 16 is
+// needed there:
+//  * ag_load_tile (stats, dq): a row is read only when row < Nk - 64 kt, 16 bytes at columns 8 ch .. 8 ch + 7 < DR of
+//    the head, inside the row; every other LDS row is written with zeros on every tile.  Rows past Nk are never
+//    touched in memory, so they may hold anything (NaN guard rows in the tests).
+//  * stats: a key past Nk gets S = AG_MASKED by a select on its index 64 kt + 16 kf + 4 g + r and then P = 0 by a select
+//    on that constant; its dP = V dO^T is an exact 0 from the zero V row, so fmaf(0, 0, dacc) adds nothing.  nkt =
+//    ceil(Nk / 64), so the last tile holds at least key 64 (nkt - 1): with exactly one key there, it is row 0 of the
+//    tile, held by the lanes g = 0, r = 0 of fragment kf = 0; dadd_max_x16x32 unites the four g of a query column, so
+//    every lane's tmax is that key's finite score and mn is finite.  l >= 1 after the tile that holds the maximum.
+//  * dkv: a lane owns key krow = 64 kb0 + 16 wave + li, per lane, not per wave: nothing is wave-uniform in Nk.  A lane
+//    past Nk reads the clamped row min(krow, Nk - 1) (a real row: finite where the data is) only to keep the MFMA
+//    operand defined; kvalid selects P = 0, so dS = 0 * (finite) = 0, its accumulator column li gets zeros (an MFMA
+//    column depends on its own B column alone, so nothing crosses to a valid key) and the store is under kvalid.
+//    ag_row_frags reads 16 bytes at columns 32 s + 8 g < DR, DR a multiple of 8: inside the row for the last valid row
+//    too.
+//  * dq: the select on 64 kt + 16 kf + 4 g + r < Nk gives P = 0, dS = 0 * (sc * 0 - D) = 0 against the zero K / V rows,
+//    and K^T dS^T reads zero rows of K for them.
+//  * ag_store_row writes 4 elements at columns 16 df + 4 g < DR of rows < Nk (dkv) or < Nq (dq) only.
+// No dependency on 16 was found: the old rule was the set of shapes the tests covered.  Nq keeps it because every site
+// has 16 queries or a multiple of 64 and the contract test pins the refusal.
+//
+// Resources per workgroup of 256 threads: LDS 2 tiles of 64 x (D + 8) halfs (18 / 26 / 26 / 42 KB for d = 40 / 80 / 96 / 160) plus
 // 512 B of row statistics in the dkv kernel; the d = 160 dkv kernel holds 2 x 16 x 160 fp32 of dK / dV per wave (80
 // registers) beside 40 of resident K / V fragments: no instantiation needs scratch (scripts/kernel_resources.py).
 #include <math.h>
@@ -384,7 +407,8 @@ struct AgEntry {
   {DR, attn_grad_stats_kernel<DR>, attn_grad_dkv_kernel<DR>, attn_grad_dq_kernel<DR>, AgGeom<DR>::SMEM_Q,        \
    AgGeom<DR>::SMEM_KV, DADD_KNAME("attn_grad_stats_kernel") "<" #DR ">", DADD_KNAME("attn_grad_dkv_kernel") "<" #DR ">", \
    DADD_KNAME("attn_grad_dq_kernel") "<" #DR ">"}
-const AgEntry AG_TABLE[] = {AG_ENTRY(40), AG_ENTRY(80), AG_ENTRY(160)};   // the head dims of the UNet's attn1 / attn2
+// the head dims of the UNet's attn1 / attn2 and, 96, of the conditioning front-end's nn.MultiheadAttention(768, 8)
+const AgEntry AG_TABLE[] = {AG_ENTRY(40), AG_ENTRY(80), AG_ENTRY(96), AG_ENTRY(160)};
 #undef AG_ENTRY
 
 const AgEntry* ag_find(int d) {
@@ -417,10 +441,10 @@ extern "C" int dadd_attn_grad_f16(const dadd_attn_grad_desc* d, void* stream) {
   DADD_REQUIRE(d->q && d->k && d->v && d->dout && d->ws, "attn_grad: null pointer");
   DADD_REQUIRE(d->dq || d->dk || d->dv, "attn_grad: no output");
   const AgEntry* e = ag_find(d->d);
-  DADD_REQUIRE(e != nullptr, "attn_grad: unsupported head dim %d (40, 80, 160)", d->d);
+  DADD_REQUIRE(e != nullptr, "attn_grad: unsupported head dim %d (40, 80, 96, 160)", d->d);
   DADD_REQUIRE(d->B > 0 && d->heads > 0, "attn_grad: empty problem");
-  DADD_REQUIRE(d->Nq >= 16 && d->Nq % 16 == 0 && d->Nk >= 16 && d->Nk % 16 == 0,
-               "attn_grad: Nq=%d and Nk=%d must be multiples of 16", d->Nq, d->Nk);
+  DADD_REQUIRE(d->Nq >= 16 && d->Nq % 16 == 0, "attn_grad: Nq=%d must be a multiple of 16", d->Nq);
+  DADD_REQUIRE(d->Nk >= 1, "attn_grad: Nk=%d must be positive", d->Nk);
   const int C = d->heads * d->d;
   DADD_REQUIRE(d->ld_q % 8 == 0 && d->ld_kv % 8 == 0 && d->ld_do % 8 == 0 && d->ld_dq % 8 == 0 && d->ld_dkv % 8 == 0,
                "attn_grad: leading dimensions must be multiples of 8");

@@ -40,6 +40,11 @@
 #define EndWgradArgs EndWgradArgs_bf16
 #define end_wgrad_kernel end_wgrad_kernel_bf16
 #define end_wgrad_finish_kernel end_wgrad_finish_kernel_bf16
+#define gelu_kernel gelu_kernel_bf16
+#define gelu_grad_kernel gelu_grad_kernel_bf16
+#define gate_tail_kernel gate_tail_kernel_bf16
+#define gate_tail_grad_kernel gate_tail_grad_kernel_bf16
+#define gate_tail_finish_kernel gate_tail_finish_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -76,6 +81,12 @@
 
 // C entry points (include/dadd_hip_attn_grad.h)
 #define dadd_attn_grad_f16 dadd_attn_grad_bf16
+
+// C entry points (include/dadd_hip_cond_grad.h)
+#define dadd_gelu_f16 dadd_gelu_bf16
+#define dadd_gelu_grad_f16 dadd_gelu_grad_bf16
+#define dadd_purifier_gate_tail_f16 dadd_purifier_gate_tail_bf16
+#define dadd_purifier_gate_tail_grad_f16 dadd_purifier_gate_tail_grad_bf16
 
 // C entry points (include/dadd_hip_dgrad.h)
 #define dadd_conv_dgrad_f16 dadd_conv_dgrad_bf16

@@ -2,6 +2,7 @@
 // HBM-bound kernels in the manner of norm.hip: wave64, 16-byte loads/stores, fp32 arithmetic, chunk partials combined
 // in a fixed order (in double where norm.hip does so), no atomics: results are bit-reproducible run to run.
 #include "dadd_common.h"
+#include "gelu_phi.h"
 #include "../../include/dadd_hip_norm_grad.h"
 
 namespace {
@@ -534,21 +535,7 @@ int lng_blocks(int M) {
   return n < LNG_MAX_BLOCKS ? n : LNG_MAX_BLOCKS;
 }
 
-// GEGLU, one thread per 8 outputs.  gelu and its derivative share the erf of dadd_gelu (Abramowitz & Stegun 7.1.26):
-// Phi(g) = (1 + erf(g/sqrt2))/2 and phi(g) = exp(-g^2/2)/sqrt(2 pi), the exponential being the one inside the erf.
-__device__ __forceinline__ void geglu_phi(float g, float& Phi, float& phi) {
-  const float z = fabsf(g) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-z * z * 1.4426950408889634f);
-  const float erf_abs = fmaf(-p * t, e, 1.0f);
-  Phi = 0.5f * (1.0f + copysignf(erf_abs, g));
-  phi = 0.39894228040143267794f * e;
-}
-
+// GEGLU, one thread per 8 outputs.  gelu and its derivative share the erf of dadd_gelu: dadd_gelu_phi (gelu_phi.h).
 __global__ __launch_bounds__(256) void geglu_kernel(const half_t* __restrict__ h, half_t* __restrict__ y, int M, int F) {
   const int fv = F >> 3;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -578,7 +565,7 @@ __global__ __launch_bounds__(256) void geglu_grad_kernel(const half_t* __restric
   for (int e = 0; e < 8; ++e) {
     const float gf = (float)g[e], df = (float)d[e];
     float Phi, phi;
-    geglu_phi(gf, Phi, phi);
+    dadd_gelu_phi(gf, Phi, phi);
     da[e] = (half_t)(df * gf * Phi);
     dg[e] = (half_t)(df * (float)a[e] * fmaf(gf, phi, Phi));
   }

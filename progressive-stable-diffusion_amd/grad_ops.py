@@ -17,8 +17,11 @@ The UNet's 4-channel ends and the loss: ``conv_in`` (fp32 NCHW latents -> 16-bit
 M-reduction GEMM of ``HipBackend.end_wgrad`` (csrc/end_grad.hip); the data gradient of ``conv_out`` is the conv_in kernel
 on dy with the weight re-laid by ``dgrad_weight_cout4`` (``HipBackend.dgrad_cout4``); ``mse_rows`` is the row-mean squared
 error with ``HipBackend.mse_rows_grad`` behind it.  A gradient now reaches every kind of UNet parameter.
-These are operators, not the training loop: still missing are the wiring into ``training_step`` and attention head dims
-other than 40 / 80 / 160.  The
+The conditioning front-end: ``gelu`` (exact-form GELU as a layer that keeps its input) and ``purifier_gate_tail``
+(LayerNorm(img - sigmoid(z) * dis)) on csrc/cond_grad.hip; with attention at d = 96 and any key count they make the
+FeaturePurifier and the image projections differentiable (``conditioning_grad``).
+These are operators, not the training loop: still missing are the wiring into ``training_step``, the AOE / ``linear_rows``
+path, attention with Nq not a multiple of 16 and head dims other than 40 / 80 / 96 / 160.  The
 optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
 arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
 in the arena's flat gradient buffer).
@@ -474,6 +477,74 @@ class _Geglu(torch.autograd.Function):
         return dh, None
 
 
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, be):
+        _check16(x, "x")
+        if x.shape[-1] % 8:
+            raise ValueError(f"gelu takes x [..., F] with F a multiple of 8, got {tuple(x.shape)}")
+        x = x.contiguous()
+        be.wait_current()
+        y = be.empty(tuple(x.shape), x.dtype)
+        be.gelu(x, y)
+        be.release_to_current()
+        ctx.save_for_backward(x)
+        ctx.be = be
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        be = ctx.be
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dy = dy.to(x.dtype).contiguous()
+        be.wait_current()
+        dx = be.empty(tuple(x.shape), x.dtype)
+        be.gelu_grad(x, dy, dx)
+        be.release_to_current()
+        return dx, None
+
+
+class _PurifierGateTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, dis, z, gamma, beta, be, eps):
+        for t, what in ((img, "img"), (dis, "dis"), (z, "z")):
+            _check16(t, what)
+        if not (img.shape == dis.shape == z.shape and img.dtype == dis.dtype == z.dtype):
+            raise ValueError(f"purifier_gate_tail takes img, dis and z of one shape and 16-bit type, got {tuple(img.shape)} "
+                             f"{img.dtype}, {tuple(dis.shape)} {dis.dtype}, {tuple(z.shape)} {z.dtype}")
+        _check_affine(gamma, beta, img.shape[-1])
+        img, dis, z, gamma, beta = (t.contiguous() for t in (img, dis, z, gamma, beta))
+        be.wait_current()
+        out = be.empty(tuple(img.shape), torch.float32)
+        be.purifier_gate_tail(img, dis, z, gamma, beta, out, eps)
+        be.release_to_current()
+        ctx.save_for_backward(img, dis, z, gamma)
+        ctx.be, ctx.eps = be, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        img, dis, z, gamma = ctx.saved_tensors
+        be = ctx.be
+        need_i, need_d, need_z, need_g, need_b = ctx.needs_input_grad[:5]
+        need_dp = need_g or need_b
+        if not (need_i or need_d or need_z or need_dp):
+            return (None,) * 7
+        dout = dout.float().contiguous()
+        c = img.shape[-1]
+        be.wait_current()
+        dimg, ddis, dz = (be.empty(tuple(img.shape), img.dtype) if need else None for need in (need_i, need_d, need_z))
+        dg = be.empty((c,), torch.float32) if need_dp else None
+        db = be.empty((c,), torch.float32) if need_dp else None
+        ws = be.empty((be.purifier_gate_tail_grad_ws_numel(img.numel() // c, c),), torch.float32) if need_dp else None
+        be.purifier_gate_tail_grad(img, dis, z, dout, gamma, dimg=dimg, ddis=ddis, dz=dz, dgamma=dg, dbeta=db, ws=ws,
+                                   eps=ctx.eps)
+        be.release_to_current()
+        return dimg, ddis, dz, dg if need_g else None, db if need_b else None, None, None
+
+
 def _attn_ws(be, q, heads):
     return be.empty((be.attn_grad_ws_numel(q.shape[0], heads, q.shape[1]),), torch.float32)
 
@@ -611,13 +682,14 @@ class _TriCrossAttention(torch.autograd.Function):
 def self_attention(be, qkv, heads):
     """qkv [B,N,3C] (q | k | v blocks of C columns) -> softmax(q k^T / sqrt(d)) v [B,N,C] per head; differentiable in qkv:
     the backward is one ``attn_grad`` call that writes dq, dk and dv into the column blocks of one [B,N,3C] tensor.
-    The backward takes d = C / heads in {40, 80, 160} and N a multiple of 16."""
+    The backward takes d = C / heads in {40, 80, 96, 160} and N a multiple of 16."""
     return _SelfAttention.apply(qkv, be, int(heads))
 
 
 def attention(be, q, k, v, heads):
     """softmax(q k^T / sqrt(d)) v with separate lengths: q [B,Nq,C], k, v [B,Nk,C] -> [B,Nq,C]; differentiable in q, k and
-    v (only the gradients that are needed are computed).  Backward: d in {40, 80, 160}, Nq and Nk multiples of 16."""
+    v (only the gradients that are needed are computed).  Backward: d in {40, 80, 96, 160}, Nq a multiple of 16, Nk any
+    positive count."""
     return _Attention.apply(q, k, v, be, int(heads))
 
 
@@ -648,3 +720,16 @@ def layer_norm(be, x, gamma, beta, eps=1e-5):
 def geglu(be, h):
     """h [..., 2F] -> h[..., :F] * gelu(h[..., F:]) (the chunk(2) order of the reference model); differentiable in h."""
     return _Geglu.apply(h, be)
+
+
+def gelu(be, x):
+    """Exact-form GELU of x [..., F] (F a multiple of 8), the activation of the conditioning front-end's MLPs;
+    differentiable in x (``HipBackend.gelu`` / ``gelu_grad``, csrc/cond_grad.hip)."""
+    return _Gelu.apply(x, be)
+
+
+def purifier_gate_tail(be, img, dis, z, gamma, beta, eps=1e-5):
+    """The FeaturePurifier's tail LayerNorm(img - sigmoid(z) * dis): img, dis and z [..., C] in one 16-bit type, z the
+    gate's pre-activation, ``gamma`` / ``beta`` the fp32 masters [C] -> fp32 [..., C].  Differentiable in all five: the
+    incoming gradient is taken in fp32, the gradients of img, dis and z come back in their 16-bit type."""
+    return _PurifierGateTail.apply(img, dis, z, gamma, beta, be, float(eps))

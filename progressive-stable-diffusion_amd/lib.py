@@ -27,6 +27,8 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            "dgrad.hip", "dgrad_bf16.hip",
            # training backward: weight / bias gradient of the 4-channel end convs and the loss gradient, and its bf16 twin
            "end_grad.hip", "end_grad_bf16.hip",
+           # training, conditioning front-end: GELU and its derivative, the purifier's gated tail and its backward, bf16 twin
+           "cond_grad.hip", "cond_grad_bf16.hip",
            # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (one source, no bf16 twin)
            "optim.hip")
 
@@ -219,6 +221,21 @@ END_GRAD_PROTOTYPES = {
     "dadd_mse_rows_grad_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, i64, vp]),
 }
 
+# every symbol include/dadd_hip_cond_grad.h declares (training kernels of the conditioning front-end, csrc/cond_grad.hip)
+_GATE_TAIL = (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp])
+_GATE_TAIL_GRAD = (C.c_int, [vp] * 11 + [C.c_int, C.c_int, f32, vp])
+COND_GRAD_PROTOTYPES = {
+    "dadd_gelu_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_gelu_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_gelu_grad_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_gelu_grad_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+    "dadd_purifier_gate_tail_f16": _GATE_TAIL,
+    "dadd_purifier_gate_tail_bf16": _GATE_TAIL,
+    "dadd_purifier_gate_tail_grad_f16": _GATE_TAIL_GRAD,
+    "dadd_purifier_gate_tail_grad_bf16": _GATE_TAIL_GRAD,
+    "dadd_purifier_gate_tail_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int]),
+}
+
 # include/dadd_hip_optim.h: the optimizer step (csrc/optim.hip)
 OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8
 OPTIM_EMA, OPTIM_P16_F16, OPTIM_P16_BF16, OPTIM_ZERO_GRAD = 1, 2, 4, 8
@@ -256,7 +273,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
         [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
                                                                        "dadd_hip_attn_grad.h", "dadd_hip_optim.h", "dadd_hip_dgrad.h",
-                                                                       "dadd_hip_end_grad.h")]
+                                                                       "dadd_hip_end_grad.h", "dadd_hip_cond_grad.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -283,7 +300,8 @@ def load() -> C.CDLL:
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
-                              **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES, **END_GRAD_PROTOTYPES}.items():
+                              **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES, **END_GRAD_PROTOTYPES,
+                              **COND_GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
