@@ -618,6 +618,73 @@ class HipBackend:
         L.check(fn(_p(img), _p(dis), _p(z), _p(dout), _p(gamma), _p(dimg), _p(ddis), _p(dz), _p(dgamma), _p(dbeta), _p(ws),
                    m, c, float(eps), self.s))
 
+    # -- training backward of the fp32 row path (csrc/rows_grad.hip)
+    def linear_rows_grad_ws_numel(self, m, k, n):
+        """fp32 elements of the ``ws`` scratch of ``linear_rows_grad`` with ``dx``: the per-strip partial sums
+        [strips][M][K]."""
+        nw = int(self.lib.dadd_linear_rows_grad_ws_floats(m, k, n))
+        if nw < 0:
+            raise ValueError(f"linear_rows_grad takes K a multiple of 8 up to 2048 and M, N >= 1 (got M {m}, K {k}, N {n})")
+        return nw
+
+    def linear_rows_grad(self, x, w, dy, *, dx=None, dw=None, db=None, ws=None, act_in=0):
+        """Backward of ``linear_rows(x, w, bias, out, act_in, 0)``: from the forward's fp32 input x [M][K] (the
+        pre-activation), w [N][K] (fp16 or fp32) and the fp32 dy [M][N]: dx [M][K], dw [N][K] (fp32 also for an fp16 w) and
+        db [N], overwritten.  ``dx`` may be None; ``dw`` and ``db`` None together, or ``db`` alone; at least one output.
+        ``dx`` needs ``ws``, fp32 scratch of ``linear_rows_grad_ws_numel`` elements (allocated here when None).  Fixed
+        summation order: bit-reproducible."""
+        m, k = x.shape
+        n = w.shape[0]
+        need = self.linear_rows_grad_ws_numel(m, k, n)
+        if act_in not in (0, 1, 2):
+            raise ValueError(f"linear_rows_grad: act_in must be 0, 1 (SiLU) or 2 (GELU), got {act_in}")
+        if dx is None and dw is None:
+            raise ValueError("linear_rows_grad: no output")
+        if dw is None and db is not None:
+            raise ValueError("linear_rows_grad: db comes with dw")
+        assert w.shape == (n, k) and w.dtype in (torch.float16, torch.float32) and w.is_contiguous()
+        assert x.dtype == torch.float32 and x.is_contiguous()
+        assert dy.dtype == torch.float32 and dy.shape == (m, n) and dy.is_contiguous()
+        for t, shape in ((dx, (m, k)), (dw, (n, k)), (db, (n,))):
+            assert t is None or (t.dtype == torch.float32 and t.shape == shape and t.is_contiguous()), shape
+        if dx is not None:
+            if ws is None:
+                ws = self.empty((need,), torch.float32)
+            assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        L.check(self.lib.dadd_linear_rows_grad_f32(_p(x), _p(w), _p(dy), _p(dx), _p(dw), _p(db), _p(ws), m, k, n, int(act_in),
+                                                   int(w.dtype == torch.float32), self.s))
+
+    def aoe_interp_grad(self, labels, dout, dbase, ddeltas):
+        """Backward of ``aoe_interp``: labels fp32 [B], dout fp32 [B][D] -> dbase [D] and ddeltas [classes - 1][D],
+        overwritten; classes <= 16.  The labels get no gradient."""
+        b, d = dout.shape
+        classes = ddeltas.shape[0] + 1
+        if not 2 <= classes <= 16:
+            raise ValueError(f"aoe_interp_grad takes 2..16 classes, got {classes}")
+        assert labels.shape == (b,) and dbase.shape == (d,) and ddeltas.shape == (classes - 1, d)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (labels, dout, dbase, ddeltas))
+        L.check(self.lib.dadd_aoe_interp_grad_f32(_p(labels), _p(dout), _p(dbase), _p(ddeltas), b, d, classes, self.s))
+
+    def rowvec_grad_ws_numel(self, b, hw, c):
+        """fp32 elements of the ``ws`` scratch of ``rowvec_grad``: the column sums of every 64-pixel chunk."""
+        nw = int(self.lib.dadd_rowvec_grad_ws_floats(b, hw, c))
+        if nw < 0:
+            raise ValueError(f"rowvec_grad takes C a multiple of 8, B in 1..65535 and HW >= 1 (got B {b}, HW {hw}, C {c})")
+        return nw
+
+    def rowvec_grad(self, dy, drow, ws=None):
+        """Gradient of the row ``EPI_ROWVEC`` adds: drow[b][c] = sum over the pixels of dy [B, ..., C] (fp16 or bf16, NHWC)
+        in fp32, overwritten.  ``ws``: fp32 scratch of ``rowvec_grad_ws_numel`` elements (allocated here when None)."""
+        b, c = dy.shape[0], dy.shape[-1]
+        hw = dy.numel() // max(b * c, 1)
+        fn = getattr(self.lib, "dadd_rowvec_grad_" + _sfx(dy))
+        need = self.rowvec_grad_ws_numel(b, hw, c)
+        if ws is None:
+            ws = self.empty((need,), torch.float32)
+        assert dy.is_contiguous() and drow.dtype == torch.float32 and drow.shape == (b, c) and drow.is_contiguous()
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        L.check(fn(_p(dy), _p(drow), _p(ws), b, hw, c, self.s))
+
     # -- training backward of attention (csrc/attn_grad.hip)
     def attn_grad_ws_numel(self, b, heads, nq):
         """fp32 elements of the ``ws`` scratch of an ``attn_grad`` call: (LSE, D) per (sample, head, query row)."""

@@ -11,9 +11,14 @@ residual additions (in the 16-bit type) and ``latents.expand`` are torch plumbin
 for the reference's 768 channels and 8 heads, against 16 AOE tokens (purifier) or the 257 CLIP tokens (resampler):
 ``grad_ops.attention`` takes any key count.  The forward of attention at d = 96 exists in fp16 only, so these run in fp16.
 
-Not here: the ``ordinal_embedder.`` path (``aoe_interp`` and the fp32 ``linear_rows`` projector have no backward yet), the
-frozen CLIP tower and the wiring into ``training_step``.  ``feature_purifier`` returns the gradient of
-its ``source_aoe`` input, where the embedder attaches.
+The fp32 row path (csrc/rows_grad.hip): ``ordinal_embedder`` restates ``AdditiveOrdinalEmbedder.__call__`` over the
+``ordinal_embedder.`` masters (``grad_ops.aoe_interp`` and two ``grad_ops.linear_rows`` on fp32 weights, fp32 throughout);
+its output, rounded to fp16, is the ``source_aoe`` of ``feature_purifier``, whose gradient of that input flows on into
+``base``, ``deltas`` and the projector.  ``time_embedding`` is the UNet's time path: sinusoid -> ``linear_1`` -> SiLU ->
+``linear_2`` -> SiLU -> every ``time_emb_proj`` in one product, fp16 weights as in ``engine.time_rows``; the column slices
+of its fp32 rows are the ``rowvec`` of the resnets' first convs (``grad_ops.conv3x3(rowvec=)``).
+
+Not here: the frozen CLIP tower and the wiring into ``training_step``.
 """
 from __future__ import annotations
 
@@ -79,3 +84,45 @@ def image_projection(be, params, image_embeds16, num_tokens=16, prefix="image_pr
     d = params[p + ".norm.weight"].shape[0]
     x = _lin(be, params, p + ".projection", image_embeds16).reshape(-1, num_tokens, d)
     return _ln(be, params, p + ".norm", x)
+
+
+def ordinal_embedder(be, params, labels, is_training=False, unconditional=False, noise_std=0.005, num_tokens=16,
+                     prefix="ordinal_embedder"):
+    """``AdditiveOrdinalEmbedder.__call__`` over the fp32 masters ``base`` [D], ``deltas`` [classes - 1][D] and
+    ``projector.{0,2}.{weight,bias}`` under ``prefix``: class interpolation of ``labels`` [B] (or a scalar), the training
+    noise (torch, ``is_training`` and ``noise_std > 0``), Linear(D, 2D) -> exact GELU -> Linear(2D, tokens * D) on the fp32
+    row kernels -> fp32 [B][tokens][D] ([tokens][D] for a scalar label).  The GELU is the second product's ``act_in``.
+    ``unconditional``: ``null_embedding`` expanded to [B][D], torch alone.  Differentiable in every master it reads; the
+    module's unused ``norm.*`` gets no gradient, as in the reference, and neither do the labels."""
+    p = prefix
+    if unconditional:
+        return params[p + ".null_embedding"].expand(labels.shape[0] if labels.dim() > 0 else 1, -1)
+    scalar = labels.dim() == 0
+    emb = G.aoe_interp(be, labels.reshape(1) if scalar else labels, params[p + ".base"], params[p + ".deltas"])
+    if is_training and noise_std > 0:
+        emb = emb + torch.randn_like(emb) * noise_std
+    h = G.linear_rows(be, emb, params[p + ".projector.0.weight"], params[p + ".projector.0.bias"])
+    out = G.linear_rows(be, h, params[p + ".projector.2.weight"], params[p + ".projector.2.bias"], act_in=2)
+    out = out.view(-1, num_tokens, emb.shape[-1])
+    return out[0] if scalar else out
+
+
+def time_embedding(be, params, t, proj_keys, dim=320, prefix="unet.unet.time_embedding"):
+    """The UNet's time path for the int64 timesteps ``t`` [B]: ``timestep_features`` (``dim`` sinusoids) -> ``linear_1``
+    -> SiLU -> ``linear_2`` -> SiLU -> ONE product over ``torch.cat`` of the ``time_emb_proj`` masters named by
+    ``proj_keys`` (key prefixes, e.g. ``unet.unet.down_blocks.0.resnets.0.time_emb_proj``) -> fp32 rows [B][sum of their
+    widths] in the order of ``proj_keys``.  The slice of a resnet's columns is the ``rowvec`` of its first conv.  The
+    matrices multiply in fp16 (``weight_dtype``), as in ``engine.time_rows``; each SiLU is the next product's ``act_in``.
+    Differentiable in ``linear_1``, ``linear_2`` and every ``time_emb_proj`` weight and bias (autograd splits the
+    gradient of the concatenation)."""
+    f16 = torch.float16
+    t = t.reshape(-1).to(torch.int64).contiguous()
+    be.wait_current()
+    feat = be.empty((t.shape[0], dim), torch.float32)
+    be.timestep_features(t, feat)
+    be.release_to_current()
+    h = G.linear_rows(be, feat, params[prefix + ".linear_1.weight"], params[prefix + ".linear_1.bias"], weight_dtype=f16)
+    h = G.linear_rows(be, h, params[prefix + ".linear_2.weight"], params[prefix + ".linear_2.bias"], act_in=1, weight_dtype=f16)
+    w = torch.cat([params[k + ".weight"] for k in proj_keys])
+    b = torch.cat([params[k + ".bias"] for k in proj_keys])
+    return G.linear_rows(be, h, w, b, act_in=1, weight_dtype=f16)

@@ -45,6 +45,8 @@
 #define gate_tail_kernel gate_tail_kernel_bf16
 #define gate_tail_grad_kernel gate_tail_grad_kernel_bf16
 #define gate_tail_finish_kernel gate_tail_finish_kernel_bf16
+#define rowvec_grad_kernel rowvec_grad_kernel_bf16
+#define rowvec_grad_finish_kernel rowvec_grad_finish_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -87,6 +89,9 @@
 #define dadd_gelu_grad_f16 dadd_gelu_grad_bf16
 #define dadd_purifier_gate_tail_f16 dadd_purifier_gate_tail_bf16
 #define dadd_purifier_gate_tail_grad_f16 dadd_purifier_gate_tail_grad_bf16
+
+// C entry points (include/dadd_hip_rows_grad.h)
+#define dadd_rowvec_grad_f16 dadd_rowvec_grad_bf16
 
 // C entry points (include/dadd_hip_dgrad.h)
 #define dadd_conv_dgrad_f16 dadd_conv_dgrad_bf16

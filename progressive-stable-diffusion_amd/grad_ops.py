@@ -20,8 +20,13 @@ error with ``HipBackend.mse_rows_grad`` behind it.  A gradient now reaches every
 The conditioning front-end: ``gelu`` (exact-form GELU as a layer that keeps its input) and ``purifier_gate_tail``
 (LayerNorm(img - sigmoid(z) * dis)) on csrc/cond_grad.hip; with attention at d = 96 and any key count they make the
 FeaturePurifier and the image projections differentiable (``conditioning_grad``).
-These are operators, not the training loop: still missing are the wiring into ``training_step``, the AOE / ``linear_rows``
-path, attention with Nq not a multiple of 16 and head dims other than 40 / 80 / 96 / 160.  The
+The fp32 row path: ``linear_rows`` (fp32 rows against an fp32 or fp16 weight with the activation on the input side: the
+AOE projector, the time-embedding MLP, the concatenated ``time_emb_proj`` layers) and ``aoe_interp`` (the AOE class table)
+on csrc/rows_grad.hip (``HipBackend.linear_rows_grad`` / ``aoe_interp_grad``); ``conv3x3(rowvec=)`` adds a resnet's time row
+in the conv's epilogue and returns its gradient (``HipBackend.rowvec_grad``).  With them every parameter the reference
+trains has a gradient on the kernels (``conditioning_grad.ordinal_embedder`` / ``time_embedding``).
+These are operators, not the training loop: still missing are the wiring into ``training_step``, attention with Nq not a
+multiple of 16 and head dims other than 40 / 80 / 96 / 160.  The
 optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
 arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
 in the arena's flat gradient buffer).
@@ -93,7 +98,7 @@ def dgrad_weight_cout4(w16: torch.Tensor) -> torch.Tensor:
     return wt
 
 
-def _forward(be, x, w, bias, taps, stride, ups):
+def _forward(be, x, w, bias, taps, stride, ups, rowvec=None):
     n = w.shape[0]
     c = x.shape[-1]
     if x.dtype not in (torch.float16, torch.bfloat16):
@@ -112,8 +117,12 @@ def _forward(be, x, w, bias, taps, stride, ups):
         out_shape4 = out_shape = (b, ho, wo, n)
     be.wait_current()
     y = be.empty(out_shape4, x.dtype)
-    be.igemm(x4, w16, y, bias=bias, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
-             flags=L.EPI_BIAS if bias is not None else 0)
+    if rowvec is None:
+        be.igemm(x4, w16, y, bias=bias, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
+                 flags=L.EPI_BIAS if bias is not None else 0)
+    else:
+        be.igemm(x4, w16, y, bias=bias, rowvec=rowvec, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
+                 flags=(L.EPI_BIAS if bias is not None else 0) | L.EPI_ROWVEC)
     be.release_to_current()
     return x4, w16, y.view(out_shape)
 
@@ -162,17 +171,58 @@ class _Product(torch.autograd.Function):
         return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, None, None, None, None)
 
 
+class _ProductRowvec(torch.autograd.Function):
+    """The stride-1 3x3 conv with the per-sample fp32 row of ``EPI_ROWVEC`` added in the epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, rowvec, be):
+        n = w.shape[0]
+        if rowvec.dtype != torch.float32 or rowvec.dim() != 2 or rowvec.shape != (x.shape[0], n) or rowvec.stride(1) != 1 \
+                or rowvec.stride(0) % 4 or rowvec.data_ptr() % 16:
+            raise ValueError(f"rowvec must be fp32 [B][N] = [{x.shape[0]}][{n}] with unit column stride, a row stride that is a "
+                             f"multiple of 4 and a 16-byte aligned start, got {tuple(rowvec.shape)} {rowvec.dtype} strides "
+                             f"{tuple(rowvec.stride())}")
+        x4, w16, y = _forward(be, x, w, bias, 9, 1, False, rowvec=rowvec.detach())
+        ctx.save_for_backward(x4, w16)
+        ctx.be, ctx.x_shape = be, x.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x4, w16 = ctx.saved_tensors
+        be = ctx.be
+        need_dx, need_dw, need_db, need_row = ctx.needs_input_grad[:4]
+        dy = dy.to(x4.dtype).contiguous()
+        dx = dw = db = drow = None
+        if need_dx or need_dw or need_db:
+            dx, dw, db = _backward(be, x4, w16, dy, 9, 1, False, need_dx, need_dw, need_db)
+        if need_row:
+            be.wait_current()
+            drow = be.empty((dy.shape[0], dy.shape[-1]), torch.float32)
+            be.rowvec_grad(dy, drow)
+            be.release_to_current()
+        return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, drow, None)
+
+
 def linear(be, x, w, bias=None):
     """y = x w^T + bias over the last axis of ``x`` ([..., C] -> [..., N]); differentiable in x, w and bias."""
     return _Product.apply(x, w, bias, be, 1, 1, False)
 
 
-def conv3x3(be, x, w, bias=None, stride=1, ups=False):
+def conv3x3(be, x, w, bias=None, stride=1, ups=False, rowvec=None):
     """3x3 convolution, padding 1, of NHWC ``x`` with ``w`` [N][9*C]; ``stride`` 1 or 2, or ``ups``: through a nearest
     2x upsample.  Differentiable in w and bias for every form; in x for stride 1 without upsample only: the resampling
-    forms with a data gradient are ``downsample2d`` and ``upsample2d``."""
+    forms with a data gradient are ``downsample2d`` and ``upsample2d``.
+    ``rowvec``: fp32 [B][N], one row per sample added to every pixel in the conv's epilogue (``EPI_ROWVEC``: the resnet's
+    time row, rounded once with the bias and the sum) - stride 1 without ``ups`` only.  It may be a strided slice of a
+    wider rows tensor (``conditioning_grad.time_embedding``); its gradient is the fp32 sum of dy over the pixels
+    (``HipBackend.rowvec_grad``).  Without ``rowvec`` nothing changes."""
     if stride not in (1, 2) or (ups and stride != 1) or x.dim() != 4:
         raise ValueError(f"conv3x3 takes NHWC x, stride 1 or 2, or ups with stride 1 (got stride {stride}, ups {ups})")
+    if rowvec is not None:
+        if stride != 1 or ups:
+            raise ValueError(f"conv3x3: rowvec goes with stride 1 and no upsample (got stride {stride}, ups {bool(ups)})")
+        return _ProductRowvec.apply(x, w, bias, rowvec, be)
     if (stride != 1 or ups) and x.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError(
             f"conv3x3(stride={stride}, ups={bool(ups)}) has no data gradient yet: the strided / upsampled dgrad kernel is "
@@ -331,6 +381,105 @@ class _MseRows(torch.autograd.Function):
         be.mse_rows_grad(pred, target, drow, dpred)
         be.release_to_current()
         return dpred, None, None
+
+
+class _LinearRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, be, act_in, weight_dtype):
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise ValueError(f"linear_rows takes fp32 rows x [M][K], got {tuple(x.shape)} {x.dtype}")
+        m, k = x.shape
+        n = w.shape[0]
+        if w.dtype != torch.float32 or w.shape != (n, k) or (bias is not None and (bias.dtype != torch.float32 or bias.shape != (n,))):
+            raise ValueError(f"w must be the fp32 master [N][{k}] and bias fp32 [N], got {tuple(w.shape)} {w.dtype}")
+        if weight_dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"linear_rows multiplies with fp32 or fp16 weights, got {weight_dtype}")
+        if act_in not in (0, 1, 2) or k % 8 or not 0 < k <= 2048 or m < 1 or n < 1:
+            raise ValueError(f"linear_rows takes act_in 0, 1 (SiLU) or 2 (GELU) and K a multiple of 8 up to 2048 (got act_in "
+                             f"{act_in}, M {m}, K {k}, N {n})")
+        x = x.contiguous()
+        wk = w.detach().to(weight_dtype).contiguous()     # rounded once (fp16) and kept for the backward
+        bias = None if bias is None else bias.detach().contiguous()
+        be.wait_current()
+        out = be.empty((m, n), torch.float32)
+        be.linear_rows(x, wk, bias, out, act_in, 0)
+        be.release_to_current()
+        ctx.save_for_backward(x, wk)
+        ctx.be, ctx.act_in = be, act_in
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wk = ctx.saved_tensors
+        be = ctx.be
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        if not (need_dx or need_dw or need_db):
+            return (None,) * 6
+        (m, k), n = x.shape, wk.shape[0]
+        dy = dy.float().contiguous()
+        be.wait_current()
+        dx = be.empty((m, k), torch.float32) if need_dx else None
+        dw = be.empty((n, k), torch.float32) if need_dw or need_db else None
+        db = be.empty((n,), torch.float32) if need_db else None
+        ws = be.empty((be.linear_rows_grad_ws_numel(m, k, n),), torch.float32) if need_dx else None
+        be.linear_rows_grad(x, wk, dy, dx=dx, dw=dw, db=db, ws=ws, act_in=ctx.act_in)
+        be.release_to_current()
+        return dx, dw if need_dw else None, db, None, None, None
+
+
+class _AoeInterp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, labels, base, deltas, be):
+        if base.dtype != torch.float32 or deltas.dtype != torch.float32 or base.dim() != 1 or deltas.dim() != 2 \
+                or deltas.shape[1] != base.shape[0] or not 1 <= deltas.shape[0] <= 15:
+            raise ValueError(f"aoe_interp takes the fp32 masters base [D] and deltas [classes - 1 <= 15][D], got "
+                             f"{tuple(base.shape)} {base.dtype} and {tuple(deltas.shape)} {deltas.dtype}")
+        if labels.dim() != 1 or labels.shape[0] < 1:
+            raise ValueError(f"aoe_interp takes labels [B], got {tuple(labels.shape)}")
+        labels = labels.detach().float().contiguous()
+        base, deltas = base.detach().contiguous(), deltas.detach().contiguous()
+        be.wait_current()
+        out = be.empty((labels.shape[0], base.shape[0]), torch.float32)
+        be.aoe_interp(labels, base, deltas, out)
+        be.release_to_current()
+        ctx.save_for_backward(labels)
+        ctx.be, ctx.classes = be, deltas.shape[0] + 1
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (labels,) = ctx.saved_tensors
+        be = ctx.be
+        _, need_b, need_d = ctx.needs_input_grad[:3]
+        if not (need_b or need_d):
+            return (None,) * 4
+        dout = dout.float().contiguous()
+        d = dout.shape[1]
+        be.wait_current()
+        dbase, ddeltas = be.empty((d,), torch.float32), be.empty((ctx.classes - 1, d), torch.float32)
+        be.aoe_interp_grad(labels, dout, dbase, ddeltas)
+        be.release_to_current()
+        return None, dbase if need_b else None, ddeltas if need_d else None, None
+
+
+def linear_rows(be, x, w, bias=None, act_in=0, weight_dtype=torch.float32):
+    """out = act_in(x) w^T + bias on the fp32 row path (``HipBackend.linear_rows``): x fp32 [M][K], ``w`` the fp32 master
+    [N][K], bias fp32 [N]; ``act_in`` 0 none, 1 SiLU, 2 exact GELU.  With ``weight_dtype=torch.float16`` (the time
+    embedding) the master is rounded once and the rounded copy kept for the backward; its gradient comes back in fp32.
+    Differentiable in x, w and bias (``HipBackend.linear_rows_grad``, csrc/rows_grad.hip).
+    The operator has no ``act_out`` on purpose: a layer's activation is applied as the NEXT layer's ``act_in``, which
+    the forward kernel supports.  The values are bit-identical to the inference path's ``act_out`` followed by ``act_in =
+    0`` (both evaluate the same fp32 function of the same fp32 sum), and the pre-activation the backward needs is then
+    simply the saved input."""
+    return _LinearRows.apply(x, w, bias, be, int(act_in), weight_dtype)
+
+
+def aoe_interp(be, labels, base, deltas):
+    """The AdditiveOrdinalEmbedder's class interpolation (``HipBackend.aoe_interp``): labels [B] (clamped to [0, classes -
+    1]), the fp32 masters ``base`` [D] and ``deltas`` [classes - 1][D] -> fp32 [B][D], the lerp between the neighbouring
+    rows of the table base + cumsum(deltas).  Differentiable in base and deltas (``HipBackend.aoe_interp_grad``); the
+    labels get no gradient."""
+    return _AoeInterp.apply(labels, base, deltas, be)
 
 
 def conv_in(be, x_nchw, w, bias=None, dtype=torch.float16):

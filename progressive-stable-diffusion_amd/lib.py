@@ -29,6 +29,8 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            "end_grad.hip", "end_grad_bf16.hip",
            # training, conditioning front-end: GELU and its derivative, the purifier's gated tail and its backward, bf16 twin
            "cond_grad.hip", "cond_grad_bf16.hip",
+           # training backward of the fp32 row path: linear_rows, aoe_interp and the EPI_ROWVEC row (the last one has the bf16 twin)
+           "rows_grad.hip", "rows_grad_bf16.hip",
            # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (one source, no bf16 twin)
            "optim.hip")
 
@@ -236,6 +238,17 @@ COND_GRAD_PROTOTYPES = {
     "dadd_purifier_gate_tail_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int]),
 }
 
+# every symbol include/dadd_hip_rows_grad.h declares (backward of the fp32 row path, csrc/rows_grad.hip)
+_ROWVEC_GRAD = (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp])
+ROWS_GRAD_PROTOTYPES = {
+    "dadd_linear_rows_grad_f32": (C.c_int, [vp] * 7 + [C.c_int] * 5 + [vp]),
+    "dadd_linear_rows_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "dadd_aoe_interp_grad_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "dadd_rowvec_grad_f16": _ROWVEC_GRAD,
+    "dadd_rowvec_grad_bf16": _ROWVEC_GRAD,
+    "dadd_rowvec_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+}
+
 # include/dadd_hip_optim.h: the optimizer step (csrc/optim.hip)
 OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8
 OPTIM_EMA, OPTIM_P16_F16, OPTIM_P16_BF16, OPTIM_ZERO_GRAD = 1, 2, 4, 8
@@ -273,7 +286,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
         [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
                                                                        "dadd_hip_attn_grad.h", "dadd_hip_optim.h", "dadd_hip_dgrad.h",
-                                                                       "dadd_hip_end_grad.h", "dadd_hip_cond_grad.h")]
+                                                                       "dadd_hip_end_grad.h", "dadd_hip_cond_grad.h", "dadd_hip_rows_grad.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -301,7 +314,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
                               **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES, **END_GRAD_PROTOTYPES,
-                              **COND_GRAD_PROTOTYPES}.items():
+                              **COND_GRAD_PROTOTYPES, **ROWS_GRAD_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
