@@ -790,6 +790,23 @@ class HipBackend:
         L.check(self.lib.dadd_optim_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(ema), _p(p16), n, group_chunks, len(group_chunks),
                                                _p(state), float(ema_weight), int(flags), int(max_blocks), self.s))
 
+    def dgrad_relayout(self, src, dst, table, n_desc, n_tiles):
+        """One launch (csrc/relayout.hip): from the flat 16-bit ``src`` (the arena's ``p16``) into the flat ``dst`` of the
+        same type, for every descriptor of ``table`` what ``grad_ops.dgrad_weight`` / ``_stride2`` / ``_ups`` / ``_cout4``
+        give for that tensor.  ``table``: the device copy (int32 words) of an array of ``lib.RelayoutDesc`` that
+        ``dadd_dgrad_relayout_plan`` has checked against both lengths; ``n_tiles`` its return value.
+        ``optim.DgradRelayout`` is the owner of table and buffer."""
+        fn = getattr(self.lib, "dadd_dgrad_relayout_" + _sfx(src, dst))
+        words = C.sizeof(L.RelayoutDesc) // 4
+        if src.dim() != 1 or dst.dim() != 1 or not src.is_contiguous() or not dst.is_contiguous():
+            raise ValueError(f"dgrad_relayout: src and dst must be flat contiguous 16-bit tensors, got {tuple(src.shape)} "
+                             f"and {tuple(dst.shape)}")
+        if table.dtype != torch.int32 or table.dim() != 1 or not table.is_contiguous() or table.numel() != n_desc * words \
+                or n_desc < 1 or n_tiles < 1:
+            raise ValueError(f"dgrad_relayout: table must be {n_desc} x {words} contiguous int32 words and n_tiles positive, "
+                             f"got {tuple(table.shape)} {table.dtype}, n_tiles {n_tiles}")
+        L.check(fn(_p(src), src.numel(), _p(dst), dst.numel(), _p(table), int(n_desc), int(n_tiles), self.s))
+
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""
         b, n, c3 = qkv.shape

@@ -18,7 +18,7 @@ its output, rounded to fp16, is the ``source_aoe`` of ``feature_purifier``, whos
 ``linear_2`` -> SiLU -> every ``time_emb_proj`` in one product, fp16 weights as in ``engine.time_rows``; the column slices
 of its fp32 rows are the ``rowvec`` of the resnets' first convs (``grad_ops.conv3x3(rowvec=)``).
 
-Not here: the frozen CLIP tower and the wiring into ``training_step``.
+Not here: the frozen CLIP tower; ``training.Trainer`` wires these into a training step.
 """
 from __future__ import annotations
 

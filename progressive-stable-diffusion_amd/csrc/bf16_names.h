@@ -47,6 +47,7 @@
 #define gate_tail_finish_kernel gate_tail_finish_kernel_bf16
 #define rowvec_grad_kernel rowvec_grad_kernel_bf16
 #define rowvec_grad_finish_kernel rowvec_grad_finish_kernel_bf16
+#define relayout_kernel relayout_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -98,3 +99,6 @@
 
 // C entry points (include/dadd_hip_end_grad.h)
 #define dadd_conv_end_wgrad_f16 dadd_conv_end_wgrad_bf16
+
+// C entry points (include/dadd_hip_relayout.h)
+#define dadd_dgrad_relayout_f16 dadd_dgrad_relayout_bf16

@@ -510,7 +510,9 @@ class DiffusionModuleWithIP:
         MSE x Min-SNR weight -> mean.  Returns the loss VALUE (a tensor without autograd history): the backward
         kernels, AdamW and EMA of BASELINE config 4 are not built, so ``loss.backward()`` raises as any leaf without
         grad does.  Keyword-only extras inject the random draws (parity tests): ``noise`` (eps), ``t``, ``drop_mask``,
-        ``latent_noise`` (the VAE posterior draw); ``is_training=False`` switches the AOE's own interpolation noise off."""
+        ``latent_noise`` (the VAE posterior draw); ``is_training=False`` switches the AOE's own interpolation noise off.
+        This method keeps that behaviour; the same forward WITH history, the backward and the optimizer are
+        ``training.Trainer(module, lr).loss()`` / ``.step()``, which stand next to it."""
         images, labels, structure_images = batch
         b = images.shape[0]
         dist = self.vae.encode(images).latent_dist
@@ -537,6 +539,8 @@ class DiffusionModuleWithIP:
         return (self._min_snr_weight(t) * base).mean()
 
     def configure_optimizers(self):
+        """Raises, as before: the module owns no trainable state.  ``training.Trainer(module, lr)`` builds the masters,
+        the reference's four parameter groups, the fused AdamW and the schedule, and runs the step."""
         raise NotImplementedError("training (backward kernels, fused AdamW, EMA: BASELINE config 4 / SURVEY.md §8f-4) is not "
                                   "built; training_step() evaluates the loss only")
 

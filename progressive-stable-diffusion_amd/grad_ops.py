@@ -25,8 +25,10 @@ AOE projector, the time-embedding MLP, the concatenated ``time_emb_proj`` layers
 on csrc/rows_grad.hip (``HipBackend.linear_rows_grad`` / ``aoe_interp_grad``); ``conv3x3(rowvec=)`` adds a resnet's time row
 in the conv's epilogue and returns its gradient (``HipBackend.rowvec_grad``).  With them every parameter the reference
 trains has a gradient on the kernels (``conditioning_grad.ordinal_embedder`` / ``time_embedding``).
-These are operators, not the training loop: still missing are the wiring into ``training_step``, attention with Nq not a
-multiple of 16 and head dims other than 40 / 80 / 96 / 160.  The
+These are operators, not the training loop: ``unet_grad`` assembles the UNet from them and ``training.Trainer`` the step;
+still missing are attention with Nq not a multiple of 16 and head dims other than 40 / 80 / 96 / 160.  The
+matrix products take ``prepared=``: the 16-bit copy and the data-gradient layout of a weight that ``optim.DgradRelayout``
+keeps, instead of a cast and a torch re-layout per call.  The
 optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
 arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
 in the arena's flat gradient buffer).
@@ -98,7 +100,27 @@ def dgrad_weight_cout4(w16: torch.Tensor) -> torch.Tensor:
     return wt
 
 
-def _forward(be, x, w, bias, taps, stride, ups, rowvec=None):
+def _wt_shape(n, c, taps, stride, ups):
+    return (c, 16 * n) if ups else (c, taps * n)
+
+
+def _check_prepared(prepared, x, w, wt_shape, what):
+    """``prepared = (w16, wt)``: the 16-bit copy of the master ``w`` (its shape) and the weight of the data gradient
+    (``wt_shape``), both contiguous, of x's type and on x's device.  Their VALUES are the caller's business
+    (``optim.DgradRelayout``)."""
+    if not isinstance(prepared, (tuple, list)) or len(prepared) != 2 or not all(isinstance(t, torch.Tensor) for t in prepared):
+        raise TypeError(f"{what}: prepared is the pair (w16, wt) of tensors, got {type(prepared).__name__}")
+    w16, wt = prepared
+    for t, shape, name in ((w16, tuple(w.shape), "w16"), (wt, tuple(wt_shape), "wt")):
+        if t.dtype != x.dtype:
+            raise TypeError(f"{what}: prepared {name} must have x's type {x.dtype}, got {t.dtype}")
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device or t.requires_grad:
+            raise ValueError(f"{what}: prepared {name} must be a contiguous {shape} tensor on {x.device} without gradient, "
+                             f"got {tuple(t.shape)} on {t.device}")
+    return w16, wt
+
+
+def _forward(be, x, w, bias, taps, stride, ups, rowvec=None, w16=None):
     n = w.shape[0]
     c = x.shape[-1]
     if x.dtype not in (torch.float16, torch.bfloat16):
@@ -106,7 +128,8 @@ def _forward(be, x, w, bias, taps, stride, ups, rowvec=None):
     if w.dtype != torch.float32 or w.shape != (n, taps * c) or (bias is not None and bias.dtype != torch.float32):
         raise ValueError(f"w must be the fp32 master [N][{taps}*{c}] and bias fp32, got {tuple(w.shape)} {w.dtype}")
     x = x.contiguous()
-    w16 = w.to(x.dtype)                         # on torch's current stream, like every producer of the inputs
+    if w16 is None:
+        w16 = w.to(x.dtype)                     # on torch's current stream, like every producer of the inputs
     if taps == 1:
         x4 = x.reshape(1, 1, -1, c)
         out_shape4, out_shape = (1, 1, x4.shape[2], n), x.shape[:-1] + (n,)
@@ -127,12 +150,11 @@ def _forward(be, x, w, bias, taps, stride, ups, rowvec=None):
     return x4, w16, y.view(out_shape)
 
 
-def _backward(be, x4, w16, dy, taps, stride, ups, need_dx, need_dw, need_db):
+def _backward(be, x4, w16, dy, taps, stride, ups, need_dx, need_dw, need_db, wt=None):
     n, c = w16.shape[0], x4.shape[-1]
     dy4 = dy.contiguous() if taps == 9 else dy.contiguous().reshape(1, 1, -1, n)
     resample = stride != 1 or ups
-    wt = None
-    if need_dx:                                            # torch plumbing, current stream
+    if need_dx and wt is None:                             # torch plumbing, current stream
         wt = dgrad_weight(w16, taps) if not resample else dgrad_weight_ups(w16) if ups else dgrad_weight_stride2(w16)
     be.wait_current()
     dx = dw = db = None
@@ -156,10 +178,13 @@ def _backward(be, x4, w16, dy, taps, stride, ups, need_dx, need_dw, need_db):
 
 class _Product(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias, be, taps, stride, ups):
-        x4, w16, y = _forward(be, x, w, bias, taps, stride, ups)
+    def forward(ctx, x, w, bias, be, taps, stride, ups, prepared=None):
+        w16 = wt = None
+        if prepared is not None:
+            w16, wt = _check_prepared(prepared, x, w, _wt_shape(w.shape[0], x.shape[-1], taps, stride, ups), "product")
+        x4, w16, y = _forward(be, x, w, bias, taps, stride, ups, w16=w16)
         ctx.save_for_backward(x4, w16)
-        ctx.be, ctx.cfg, ctx.x_shape = be, (taps, stride, ups), x.shape
+        ctx.be, ctx.cfg, ctx.x_shape, ctx.wt = be, (taps, stride, ups), x.shape, wt
         return y
 
     @staticmethod
@@ -167,24 +192,27 @@ class _Product(torch.autograd.Function):
         x4, w16 = ctx.saved_tensors
         taps, stride, ups = ctx.cfg
         need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
-        dx, dw, db = _backward(ctx.be, x4, w16, dy.to(x4.dtype), taps, stride, ups, need_dx, need_dw, need_db)
-        return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, None, None, None, None)
+        dx, dw, db = _backward(ctx.be, x4, w16, dy.to(x4.dtype), taps, stride, ups, need_dx, need_dw, need_db, wt=ctx.wt)
+        return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, None, None, None, None, None)
 
 
 class _ProductRowvec(torch.autograd.Function):
     """The stride-1 3x3 conv with the per-sample fp32 row of ``EPI_ROWVEC`` added in the epilogue."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, rowvec, be):
+    def forward(ctx, x, w, bias, rowvec, be, prepared=None):
         n = w.shape[0]
         if rowvec.dtype != torch.float32 or rowvec.dim() != 2 or rowvec.shape != (x.shape[0], n) or rowvec.stride(1) != 1 \
                 or rowvec.stride(0) % 4 or rowvec.data_ptr() % 16:
             raise ValueError(f"rowvec must be fp32 [B][N] = [{x.shape[0]}][{n}] with unit column stride, a row stride that is a "
                              f"multiple of 4 and a 16-byte aligned start, got {tuple(rowvec.shape)} {rowvec.dtype} strides "
                              f"{tuple(rowvec.stride())}")
-        x4, w16, y = _forward(be, x, w, bias, 9, 1, False, rowvec=rowvec.detach())
+        w16 = wt = None
+        if prepared is not None:
+            w16, wt = _check_prepared(prepared, x, w, _wt_shape(n, x.shape[-1], 9, 1, False), "conv3x3")
+        x4, w16, y = _forward(be, x, w, bias, 9, 1, False, rowvec=rowvec.detach(), w16=w16)
         ctx.save_for_backward(x4, w16)
-        ctx.be, ctx.x_shape = be, x.shape
+        ctx.be, ctx.x_shape, ctx.wt = be, x.shape, wt
         return y
 
     @staticmethod
@@ -195,59 +223,70 @@ class _ProductRowvec(torch.autograd.Function):
         dy = dy.to(x4.dtype).contiguous()
         dx = dw = db = drow = None
         if need_dx or need_dw or need_db:
-            dx, dw, db = _backward(be, x4, w16, dy, 9, 1, False, need_dx, need_dw, need_db)
+            dx, dw, db = _backward(be, x4, w16, dy, 9, 1, False, need_dx, need_dw, need_db, wt=ctx.wt)
         if need_row:
             be.wait_current()
             drow = be.empty((dy.shape[0], dy.shape[-1]), torch.float32)
             be.rowvec_grad(dy, drow)
             be.release_to_current()
-        return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, drow, None)
+        return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, drow, None, None)
 
 
-def linear(be, x, w, bias=None):
-    """y = x w^T + bias over the last axis of ``x`` ([..., C] -> [..., N]); differentiable in x, w and bias."""
-    return _Product.apply(x, w, bias, be, 1, 1, False)
+def linear(be, x, w, bias=None, prepared=None):
+    """y = x w^T + bias over the last axis of ``x`` ([..., C] -> [..., N]); differentiable in x, w and bias.
+    ``prepared``: the pair ``(w16, wt)`` of ``optim.DgradRelayout.prepared(name)`` - the 16-bit copy of ``w`` that the
+    optimizer step already wrote and the weight of the data gradient that one re-layout launch wrote (here
+    ``dgrad_weight(w16, 1)``).  The forward then reads ``w16`` instead of casting ``w``, the backward ``wt`` instead of
+    re-laying; the gradients still go to the master ``w``.  The same keyword, with the layout of their own helper, is taken
+    by ``conv3x3`` (stride 1), ``downsample2d``, ``upsample2d`` and ``conv_out``.  Without it nothing changes."""
+    return _Product.apply(x, w, bias, be, 1, 1, False, prepared)
 
 
-def conv3x3(be, x, w, bias=None, stride=1, ups=False, rowvec=None):
+def conv3x3(be, x, w, bias=None, stride=1, ups=False, rowvec=None, prepared=None):
     """3x3 convolution, padding 1, of NHWC ``x`` with ``w`` [N][9*C]; ``stride`` 1 or 2, or ``ups``: through a nearest
     2x upsample.  Differentiable in w and bias for every form; in x for stride 1 without upsample only: the resampling
     forms with a data gradient are ``downsample2d`` and ``upsample2d``.
     ``rowvec``: fp32 [B][N], one row per sample added to every pixel in the conv's epilogue (``EPI_ROWVEC``: the resnet's
     time row, rounded once with the bias and the sum) - stride 1 without ``ups`` only.  It may be a strided slice of a
     wider rows tensor (``conditioning_grad.time_embedding``); its gradient is the fp32 sum of dy over the pixels
-    (``HipBackend.rowvec_grad``).  Without ``rowvec`` nothing changes."""
+    (``HipBackend.rowvec_grad``).  Without ``rowvec`` nothing changes.
+    ``prepared``: as in ``linear``, with ``wt = dgrad_weight(w16, 9)``; stride 1 without ``ups`` only."""
     if stride not in (1, 2) or (ups and stride != 1) or x.dim() != 4:
         raise ValueError(f"conv3x3 takes NHWC x, stride 1 or 2, or ups with stride 1 (got stride {stride}, ups {ups})")
     if rowvec is not None:
         if stride != 1 or ups:
             raise ValueError(f"conv3x3: rowvec goes with stride 1 and no upsample (got stride {stride}, ups {bool(ups)})")
-        return _ProductRowvec.apply(x, w, bias, rowvec, be)
+        return _ProductRowvec.apply(x, w, bias, rowvec, be, prepared)
+    if prepared is not None and (stride != 1 or ups):
+        raise ValueError("conv3x3: prepared goes with stride 1 and no upsample; the resampling forms that take it are "
+                         "downsample2d and upsample2d")
     if (stride != 1 or ups) and x.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError(
             f"conv3x3(stride={stride}, ups={bool(ups)}) has no data gradient yet: the strided / upsampled dgrad kernel is "
             "missing; pass x.detach() to get the weight and bias gradients")
-    return _Product.apply(x, w, bias, be, 9, stride, bool(ups))
+    return _Product.apply(x, w, bias, be, 9, stride, bool(ups), prepared)
 
 
-def downsample2d(be, x, w, bias=None):
+def downsample2d(be, x, w, bias=None, prepared=None):
     """diffusers' ``Downsample2D`` conv: 3x3, stride 2, padding 1 of NHWC ``x`` [B,H,W,C] with ``w`` [N][9*C] ->
     [B,(H-1)//2+1,(W-1)//2+1,N]; odd maps are legal.  Differentiable in x, w and bias: forward and weight / bias gradient
     are those of ``conv3x3(stride=2)``, the data gradient is the parity-class gather-GEMM of csrc/dgrad.hip on the
-    weight re-laid by ``dgrad_weight_stride2`` (9 tap products per input pixel, none on a zero of a dilated dy)."""
+    weight re-laid by ``dgrad_weight_stride2`` (9 tap products per input pixel, none on a zero of a dilated dy).
+    ``prepared``: as in ``linear``, with ``wt = dgrad_weight_stride2(w16)``."""
     if x.dim() != 4:
         raise ValueError(f"downsample2d takes NHWC x, got {tuple(x.shape)}")
-    return _Product.apply(x, w, bias, be, 9, 2, False)
+    return _Product.apply(x, w, bias, be, 9, 2, False, prepared)
 
 
-def upsample2d(be, x, w, bias=None):
+def upsample2d(be, x, w, bias=None, prepared=None):
     """diffusers' ``Upsample2D``: nearest 2x upsample, then 3x3 conv, padding 1, of NHWC ``x`` [B,H,W,C] with ``w``
     [N][9*C] -> [B,2H,2W,N]; the upsampled tensor is never materialised.  Differentiable in x, w and bias: forward and
     weight / bias gradient are those of ``conv3x3(ups=True)``, the data gradient is csrc/dgrad.hip on the 16 pre-summed
-    taps of ``dgrad_weight_ups`` (summed in fp32, rounded once: one rounding more than the forward has)."""
+    taps of ``dgrad_weight_ups`` (summed in fp32, rounded once: one rounding more than the forward has).
+    ``prepared``: as in ``linear``, with ``wt = dgrad_weight_ups(w16)``."""
     if x.dim() != 4:
         raise ValueError(f"upsample2d takes NHWC x, got {tuple(x.shape)}")
-    return _Product.apply(x, w, bias, be, 9, 1, True)
+    return _Product.apply(x, w, bias, be, 9, 1, True, prepared)
 
 
 def _end_wgrad(be, thin, wide, dw_shape, nb, mode, need_db):
@@ -264,7 +303,7 @@ def _end_wgrad(be, thin, wide, dw_shape, nb, mode, need_db):
 
 class _ConvIn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias, be, dtype):
+    def forward(ctx, x, w, bias, be, dtype, data_grad=False):
         if x.dim() != 4 or x.dtype != torch.float32 or not 1 <= x.shape[1] <= 4:
             raise ValueError(f"conv_in takes fp32 NCHW x with 1..4 channels, got {tuple(x.shape)} {x.dtype}")
         b, ct, h, wd = x.shape
@@ -280,36 +319,45 @@ class _ConvIn(torch.autograd.Function):
                              "forward alone)")
         x = x.contiguous()
         w8 = torch.zeros((n, 9, 8), dtype=dtype, device=w.device)     # pack_conv_cin8 of the rounded master
-        w8[:, :, :ct] = w.detach().reshape(n, 9, ct).to(dtype)
+        w16 = w.detach().reshape(n, 9, ct).to(dtype)
+        w8[:, :, :ct] = w16
         bias = None if bias is None else bias.detach().contiguous()
         be.wait_current()
         y = be.empty((b, h, wd, n), dtype)
         be.conv_in_nchw(x, w8, bias, y)
         be.release_to_current()
-        ctx.save_for_backward(x)
-        ctx.be = be
+        need_dx = bool(data_grad) and ctx.needs_input_grad[0]
+        ctx.save_for_backward(x, w16 if need_dx else None)
+        ctx.be, ctx.need_dx = be, need_dx
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
+        x, w16 = ctx.saved_tensors
         be = ctx.be
         _, need_dw, need_db = ctx.needs_input_grad[:3]
-        if not (need_dw or need_db):
-            return (None,) * 5
+        need_dx = ctx.need_dx
+        if not (need_dx or need_dw or need_db):
+            return (None,) * 6
         ct, n = x.shape[1], dy.shape[-1]
         dy = dy.contiguous()
+        wt = w16.flip(1).permute(2, 1, 0).contiguous() if need_dx else None     # [Ct][8 - tap][N]: torch plumbing, tiny
         be.wait_current()
-        dw8, db = _end_wgrad(be, x, dy, (n, 9, 8), n, L.END_WGRAD_IN, need_db)
-        with be.ctx():
-            dw = dw8[:, :, :ct].reshape(n, 9 * ct)
+        dx = dw = db = None
+        if need_dx:                      # the conv_out kernel on dy with the flipped, transposed weight
+            dx = be.empty(tuple(x.shape), torch.float32)
+            be.conv_cout4(dy.to(w16.dtype), wt, None, dx, mode=0)
+        if need_dw or need_db:
+            dw8, db = _end_wgrad(be, x, dy, (n, 9, 8), n, L.END_WGRAD_IN, need_db)
+            with be.ctx():
+                dw = dw8[:, :, :ct].reshape(n, 9 * ct)
         be.release_to_current()
-        return None, dw if need_dw else None, db, None, None
+        return dx, dw if need_dw else None, db, None, None, None
 
 
 class _ConvOut(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias, be):
+    def forward(ctx, x, w, bias, be, prepared=None):
         _check16(x, "x")
         if x.dim() != 4:
             raise ValueError(f"conv_out takes NHWC x, got {tuple(x.shape)}")
@@ -322,14 +370,18 @@ class _ConvOut(torch.autograd.Function):
             raise ValueError(f"conv_out: the weight / bias gradient takes C a multiple of 64, got {c} (detach w and bias for a "
                              "forward and a data gradient alone)")
         x = x.contiguous()
-        w16 = w.detach().to(x.dtype).contiguous()   # [Co][9*C] is pack_conv_cout4's [Co][9][C]
+        wt = None
+        if prepared is not None:
+            w16, wt = _check_prepared(prepared, x, w, (c, 9, 8), "conv_out")
+        else:
+            w16 = w.detach().to(x.dtype).contiguous()   # [Co][9*C] is pack_conv_cout4's [Co][9][C]
         bias = None if bias is None else bias.detach().contiguous()
         be.wait_current()
         y = be.empty((b, co, h, wd), torch.float32)
         be.conv_cout4(x, w16.view(co, 9, c), bias, y, mode=0)
         be.release_to_current()
         ctx.save_for_backward(x, w16)
-        ctx.be = be
+        ctx.be, ctx.wt = be, wt
         return y
 
     @staticmethod
@@ -338,10 +390,12 @@ class _ConvOut(torch.autograd.Function):
         be = ctx.be
         need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
         if not (need_dx or need_dw or need_db):
-            return (None,) * 4
+            return (None,) * 5
         co, c = w16.shape[0], x.shape[-1]
         dy = dy.float().contiguous()
-        wt = dgrad_weight_cout4(w16) if need_dx else None      # torch plumbing, current stream
+        wt = ctx.wt
+        if need_dx and wt is None:
+            wt = dgrad_weight_cout4(w16)                       # torch plumbing, current stream
         be.wait_current()
         dx = dw = db = None
         if need_dx:
@@ -351,7 +405,7 @@ class _ConvOut(torch.autograd.Function):
             dw, db = _end_wgrad(be, dy, x, (co, 9, c), co, L.END_WGRAD_OUT, need_db)
             dw = dw.view(co, 9 * c)
         be.release_to_current()
-        return dx, dw if need_dw else None, db, None
+        return dx, dw if need_dw else None, db, None, None
 
 
 class _MseRows(torch.autograd.Function):
@@ -482,24 +536,26 @@ def aoe_interp(be, labels, base, deltas):
     return _AoeInterp.apply(labels, base, deltas, be)
 
 
-def conv_in(be, x_nchw, w, bias=None, dtype=torch.float16):
+def conv_in(be, x_nchw, w, bias=None, dtype=torch.float16, data_grad=False):
     """The UNet's conv_in: 3x3, padding 1, of the fp32 NCHW latents ``x_nchw`` [B, Ct <= 4, H, W] with the fp32 master
     ``w`` [N][9*Ct] -> ``dtype`` (fp16 or bf16) NHWC [B,H,W,N]; the latents are rounded to ``dtype`` in registers
     (``HipBackend.conv_in_nchw``).  Differentiable in w and bias (``HipBackend.end_wgrad``, IN mode; N a multiple of
-    64: with a trainable w or bias any other N is refused by the forward, N a multiple of 8 suffices without).  The latents are data: there is no gradient of ``x_nchw``."""
-    if x_nchw.requires_grad and torch.is_grad_enabled():
+    64: with a trainable w or bias any other N is refused by the forward, N a multiple of 8 suffices without).  The latents are data: there is no gradient of ``x_nchw``.
+    ``data_grad=True`` lifts that for a caller that asks (a gradient check of the whole UNet): the fp32 NCHW gradient of
+    ``x_nchw`` is then ``HipBackend.conv_cout4`` (the conv_out kernel) on dy with the flipped, transposed weight."""
+    if x_nchw.requires_grad and torch.is_grad_enabled() and not data_grad:
         raise NotImplementedError("conv_in has no data gradient: the latents are data; pass x_nchw.detach() to get the "
                                   "weight and bias gradients")
-    return _ConvIn.apply(x_nchw, w, bias, be, dtype)
+    return _ConvIn.apply(x_nchw, w, bias, be, dtype, bool(data_grad))
 
 
-def conv_out(be, x, w, bias=None):
+def conv_out(be, x, w, bias=None, prepared=None):
     """The UNet's conv_out: 3x3, padding 1, of 16-bit NHWC ``x`` [B,H,W,C] with the fp32 master ``w`` [Co <= 4][9*C] ->
     fp32 NCHW [B,Co,H,W] (``HipBackend.conv_cout4``, mode 0).  Differentiable in x, w and bias: the incoming fp32
     gradient is rounded to ``x.dtype`` in registers by both backward kernels (``HipBackend.dgrad_cout4`` on the weight of
     ``dgrad_weight_cout4``; ``HipBackend.end_wgrad``, OUT mode; C a multiple of 64: with a trainable w or bias any other C is refused by the
-    forward)."""
-    return _ConvOut.apply(x, w, bias, be)
+    forward).  ``prepared``: as in ``linear``, with ``wt = dgrad_weight_cout4(w16)``."""
+    return _ConvOut.apply(x, w, bias, be, prepared)
 
 
 def mse_rows(be, pred, target):

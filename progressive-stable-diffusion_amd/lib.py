@@ -32,7 +32,9 @@ SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ff
            # training backward of the fp32 row path: linear_rows, aoe_interp and the EPI_ROWVEC row (the last one has the bf16 twin)
            "rows_grad.hip", "rows_grad_bf16.hip",
            # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (one source, no bf16 twin)
-           "optim.hip")
+           "optim.hip",
+           # training: one-launch re-layout of the 16-bit weights for the data gradients, and its bf16 twin
+           "relayout.hip", "relayout_bf16.hip")
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -276,6 +278,27 @@ OPTIM_PROTOTYPES = {
                                         C.c_int, C.c_int, vp]),
 }
 
+# include/dadd_hip_relayout.h: the one-launch re-layout of the data-gradient weights (csrc/relayout.hip)
+RELAYOUT_T, RELAYOUT_S2, RELAYOUT_UPS, RELAYOUT_COUT4 = 0, 1, 2, 3
+RELAYOUT_TILE = 64
+
+
+class RelayoutDesc(C.Structure):
+    """Mirror of ``dadd_relayout_desc``."""
+    _fields_ = [("src_off", C.c_longlong), ("dst_off", C.c_longlong)] + \
+               [(n, i32) for n in ("N", "C", "kind", "taps", "tile0", "reserved")]
+
+
+# every symbol include/dadd_hip_relayout.h declares
+_RELAYOUT = (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, vp])
+RELAYOUT_PROTOTYPES = {
+    "dadd_relayout_tiles": (C.c_longlong, [C.c_int] * 4),
+    "dadd_relayout_dst_numel": (C.c_longlong, [C.c_int] * 4),
+    "dadd_dgrad_relayout_plan": (C.c_longlong, [C.POINTER(RelayoutDesc), C.c_int, C.c_longlong, C.c_longlong]),
+    "dadd_dgrad_relayout_f16": _RELAYOUT,
+    "dadd_dgrad_relayout_bf16": _RELAYOUT,
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -286,7 +309,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
         [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
                                                                        "dadd_hip_attn_grad.h", "dadd_hip_optim.h", "dadd_hip_dgrad.h",
-                                                                       "dadd_hip_end_grad.h", "dadd_hip_cond_grad.h", "dadd_hip_rows_grad.h")]
+                                                                       "dadd_hip_end_grad.h", "dadd_hip_cond_grad.h", "dadd_hip_rows_grad.h",
+                                                                       "dadd_hip_relayout.h")]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -314,7 +338,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
                               **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES, **END_GRAD_PROTOTYPES,
-                              **COND_GRAD_PROTOTYPES, **ROWS_GRAD_PROTOTYPES}.items():
+                              **COND_GRAD_PROTOTYPES, **ROWS_GRAD_PROTOTYPES, **RELAYOUT_PROTOTYPES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -9,13 +9,17 @@ owns the device-resident state block (step count, loss scale, per-group constant
 ``reference_param_groups`` restates the grouping of the reference's ``configure_optimizers`` (src/models/
 diffusion_module_ip.py: UNet and ordinal embedder at ``lr``, image projection and feature purifier at ``2 * lr``).
 
-Not wired into ``DiffusionModuleWithIP`` yet: ``configure_optimizers()`` still raises.
+``DgradRelayout`` stands next to the arena: it owns the second 16-bit buffer that holds every weight in the layout its
+data gradient reads, refreshed from ``p16`` by one launch of csrc/relayout.hip after each optimizer step.
+
+``training.Trainer`` wires these into a training step; ``DiffusionModuleWithIP.configure_optimizers()`` itself still
+raises.
 """
 from __future__ import annotations
 
 import ctypes as C
 from collections import OrderedDict
-from typing import Dict, List, Mapping, Optional, Sequence
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -147,6 +151,122 @@ class ParamArena:
                 raise ValueError(f"{k}: expected an fp32 leaf of shape {tuple(self.shapes[k])}, got {tuple(t.shape)} {t.dtype}")
             t.data = self.param(k)
             t.grad = self.grad(k)
+
+
+RELAYOUT_KINDS = {"T": L.RELAYOUT_T, "S2": L.RELAYOUT_S2, "UPS": L.RELAYOUT_UPS, "COUT4": L.RELAYOUT_COUT4}
+
+
+def relayout_plan(items: Sequence[Tuple[int, int, int, int, str, int]], src_numel: int, dst_numel: int):
+    """The descriptor table of one re-layout launch.  ``items``: ``(src_off, dst_off, N, C, kind, taps)`` per tensor, in
+    ascending ``dst_off`` order; ``kind`` one of ``RELAYOUT_KINDS``.  -> ``(table, n_tiles)``: a ctypes array of
+    ``lib.RelayoutDesc`` with ``tile0`` filled in and the grid of the launch.  The library checks the contract of
+    include/dadd_hip_relayout.h (alignment, multiples of 8, every range inside its array, destinations disjoint) and a
+    breach is a ``ValueError``; nothing here needs a GPU."""
+    if not items:
+        raise ValueError("relayout_plan: no tensors")
+    table = (L.RelayoutDesc * len(items))()
+    for d, (src_off, dst_off, n, c, kind, taps) in zip(table, items):
+        if kind not in RELAYOUT_KINDS:
+            raise ValueError(f"relayout_plan: kind {kind!r} is none of {sorted(RELAYOUT_KINDS)}")
+        d.src_off, d.dst_off, d.N, d.C, d.kind, d.taps = int(src_off), int(dst_off), int(n), int(c), RELAYOUT_KINDS[kind], int(taps)
+    lib = L.load()
+    n_tiles = lib.dadd_dgrad_relayout_plan(table, len(items), int(src_numel), int(dst_numel))
+    if n_tiles < 0:
+        raise ValueError((lib.dadd_last_error() or b"").decode())
+    return table, int(n_tiles)
+
+
+def relayout_dst_numel(kind: str, taps: int, n: int, c: int) -> int:
+    """Elements of the re-laid copy of an ``[N][taps*C]`` weight of ``kind``; ``ValueError`` outside the contract."""
+    r = L.load().dadd_relayout_dst_numel(RELAYOUT_KINDS.get(kind, -1), int(taps), int(n), int(c))
+    if r < 0:
+        raise ValueError(f"relayout: kind {kind!r}, taps {taps}, N {n}, C {c} is outside the contract (N and C multiples of "
+                         "8; COUT4: N 1..4; taps 1 or 9 for T, 9 otherwise)")
+    return int(r)
+
+
+class DgradRelayout:
+    """Owner of the data-gradient layouts of an arena's weights: a flat 16-bit buffer ``wt`` beside ``arena.p16`` and the
+    device-resident descriptor table of the launch that fills it.
+
+    ``entries``: ``(name, kind)`` or ``(name, kind, taps)`` per weight; the arena holds it as ``[N][taps*C]``.  ``kind``:
+    ``"T"`` (``grad_ops.dgrad_weight``; ``taps`` 1 unless given as 9), ``"S2"`` (``dgrad_weight_stride2``), ``"UPS"``
+    (``dgrad_weight_ups``), ``"COUT4"`` (``dgrad_weight_cout4``).  Buffer and table are allocated once; ``refresh()`` is
+    one launch on the backend's stream, ordered like ``FusedAdamW.step``.  ``w16(name)`` / ``wt(name)`` are the views a
+    ``grad_ops`` product takes as ``prepared=``.  ``be=None`` gives an owner that holds the table but cannot launch."""
+
+    def __init__(self, be, arena: ParamArena, entries: Sequence[tuple]):
+        if arena.p16 is None:
+            raise RuntimeError("DgradRelayout reads the arena's 16-bit working copy (working_dtype / ensure_p16)")
+        if be is not None and arena.device != be.device:
+            raise ValueError(f"the arena lives on {arena.device}, the backend on {be.device}")
+        self.be, self.arena = be, arena
+        self.kinds: Dict[str, Tuple[str, int]] = {}
+        self.offsets: Dict[str, int] = {}
+        self.shapes: Dict[str, Tuple[int, ...]] = {}
+        items, off = [], 0
+        for e in entries:
+            name, kind = e[0], e[1]
+            taps = int(e[2]) if len(e) > 2 else (1 if kind == "T" else 9)
+            if name not in arena.offsets:
+                raise KeyError(f"{name} is not in the arena")
+            if name in self.kinds:
+                raise ValueError(f"{name} is listed twice")
+            shape = arena.shapes[name]
+            if len(shape) != 2 or shape[1] % taps:
+                raise ValueError(f"{name}: expected the library layout [N][{taps}*C], got {tuple(shape)}")
+            n, c = int(shape[0]), int(shape[1]) // taps
+            numel = relayout_dst_numel(kind, taps, n, c)
+            self.kinds[name], self.offsets[name] = (kind, taps), off
+            self.shapes[name] = (c, 9, 8) if kind == "COUT4" else (c, numel // c)
+            items.append((arena.offsets[name], off, n, c, kind, taps))
+            off += _round_up(numel, _ALIGN)
+        self.numel = off
+        self._table, self.n_tiles = relayout_plan(items, arena.numel, self.numel)
+        self.n_desc = len(items)
+        self.buf = torch.zeros(self.numel, dtype=arena.p16.dtype, device=arena.device)
+        words = torch.frombuffer(bytearray(bytes(self._table)), dtype=torch.int32)
+        self.table = torch.zeros(words.numel(), dtype=torch.int32, device=arena.device)
+        if be is not None:
+            be.wait_current()
+            be.copy_(self.table, words)
+            be.release_to_current()
+        else:
+            self.table.copy_(words)
+
+    def launch(self) -> None:
+        """The one launch on the backend's stream, nothing else: what a graph capture records."""
+        if self.be is None:
+            raise RuntimeError("DgradRelayout was built without a backend: it holds the table but cannot launch")
+        self.be.dgrad_relayout(self.arena.p16, self.buf, self.table, self.n_desc, self.n_tiles)
+
+    def refresh(self) -> None:
+        """Re-lay every listed weight from the arena's current ``p16``.  Ordered after torch's current stream and before
+        what it does next, like ``FusedAdamW.step``; no host sync."""
+        if self.be is None:
+            raise RuntimeError("DgradRelayout was built without a backend: it holds the table but cannot launch")
+        capturing = self.be._capturing
+        if not capturing:
+            self.be.wait_current()
+        self.launch()
+        if not capturing:
+            self.be.release_to_current()
+
+    def w16(self, name: str) -> torch.Tensor:
+        """The 16-bit working copy of ``name``: ``arena.param16``."""
+        return self.arena.param16(name)
+
+    def wt(self, name: str) -> torch.Tensor:
+        """The re-laid copy of ``name`` as of the last ``refresh()``: ``[C][slabs*N]``, COUT4 ``[C][9][8]``."""
+        off, shape = self.offsets[name], self.shapes[name]
+        numel = 1
+        for v in shape:
+            numel *= v
+        return self.buf[off:off + numel].view(shape)
+
+    def prepared(self, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(w16, wt)`` of ``name``: the ``prepared=`` argument of the ``grad_ops`` products."""
+        return self.w16(name), self.wt(name)
 
 
 def reference_param_groups(names: Sequence[str], lr: float, weight_decay: float = 0.0) -> List[dict]:
