@@ -175,6 +175,38 @@ class HipBackend:
     def release_to_current(self):
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
+    # ------------------------------------------------------------------ checks the training ops share
+    @staticmethod
+    def _scratch_numel(fn, args, message):
+        """fp32 elements of an op's scratch from its ``dadd_*_floats`` query; the library answers -1 for sizes the op does
+        not take, which raises ``ValueError(message.format(*args))``."""
+        n = int(fn(*args))
+        if n < 0:
+            raise ValueError(message.format(*args))
+        return n
+
+    def _splitm(self, m, tiles):
+        """Default slices of an ``m``-row reduction behind ``tiles`` output tiles: about 2 workgroups per CU, at least 64
+        rows per slice: ``max(1, min(ceil(2 * CUs / tiles), ceil(m / 64)))``."""
+        if self._n_cu is None:
+            self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        return max(1, min(-(-2 * self._n_cu // tiles), -(-m // 64)))
+
+    @staticmethod
+    def _param_grad_checks(dgamma, dbeta, c, ws, need):
+        """The parameter-gradient arguments of a norm backward, as three answers the caller raises on in its own words:
+        dgamma and dbeta are both given or both None; each one given is contiguous fp32 [C]; ``ws`` is contiguous fp32
+        with at least ``need`` elements."""
+        together = (dgamma is None) == (dbeta is None)
+        shaped = all(t is None or (t.dtype == torch.float32 and t.numel() == c and t.is_contiguous()) for t in (dgamma, dbeta))
+        ws_ok = ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need
+        return together, shaped, ws_ok
+
+    @staticmethod
+    def _pointwise_width(op, f):
+        if f % 8 or f == 0:
+            raise ValueError(f"{op}: F = {f} must be a positive multiple of 8")
+
     # ------------------------------------------------------------------ ops
     def pack_latents(self, x, out, scale=1.0, mat=None, vec=None):
         b, c, h, w = x.shape
@@ -257,10 +289,7 @@ class HipBackend:
         usually far fewer than the device has CUs, and a reduction of M rows behind each; split it until the launch has
         about 2 workgroups per CU, every slice keeping at least 64 rows (the kernel itself takes slices down to one 32-row
         MFMA step, ``splitm <= ceil(M/32)``)."""
-        if self._n_cu is None:
-            self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        tiles = -(-n // 64) * taps * (c // 64)
-        return max(1, min(-(-2 * self._n_cu // tiles), -(-m // 64)))
+        return self._splitm(m, -(-n // 64) * taps * (c // 64))
 
     @staticmethod
     def wgrad_partial_numel(splitm, n, c, taps=1):
@@ -353,18 +382,13 @@ class HipBackend:
         36 thin columns) and a reduction of M = B*H*W pixels behind each; split it until the launch has about 2 workgroups
         per CU, every slice keeping at least 64 pixels (the kernel itself takes slices down to one 32-pixel MFMA step,
         ``splitm <= ceil(M/32)``): ``max(1, min(ceil(2 * CUs / (Cw/64)), ceil(M/64)))``, the rule of ``wgrad_splitm``."""
-        if self._n_cu is None:
-            self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        tiles = max(1, cw // 64)
-        return max(1, min(-(-2 * self._n_cu // tiles), -(-m // 64)))
+        return self._splitm(m, max(1, cw // 64))
 
     def end_wgrad_partial_numel(self, splitm, ct, cw, mode):
         """fp32 elements of the ``partial`` scratch of an ``end_wgrad`` call (nothing for ``splitm == 1``): per slice dw
         in its final layout and the bias sums."""
-        n = int(self.lib.dadd_end_wgrad_partial_floats(int(mode), int(ct), int(cw), int(splitm)))
-        if n < 0:
-            raise ValueError(f"end_wgrad takes mode 0 or 1, Ct in 1..4 and Cw a multiple of 64 (got mode {mode}, Ct {ct}, Cw {cw})")
-        return n
+        return self._scratch_numel(self.lib.dadd_end_wgrad_partial_floats, (int(mode), int(ct), int(cw), int(splitm)),
+                                   "end_wgrad takes mode 0 or 1, Ct in 1..4 and Cw a multiple of 64 (got mode {}, Ct {}, Cw {})")
 
     def end_wgrad(self, thin, wide, dw, *, dbias=None, mode, splitm=None, partial=None):
         """Weight (and bias) gradient of a 4-channel end conv (3x3, stride 1, padding 1), fp32, overwritten.  ``thin`` is
@@ -460,11 +484,9 @@ class HipBackend:
     def groupnorm_grad_ws_numel(self, b, hw, c, groups):
         """fp32 elements of the ``ws`` scratch of a ``groupnorm_grad`` call: the chunk partials of the statistics, of
         s1 / s2 and of the channel sums (include/dadd_hip_norm_grad.h)."""
-        n = int(self.lib.dadd_groupnorm_grad_ws_floats(b, hw, c, groups))
-        if n < 0:
-            raise ValueError(f"groupnorm_grad takes C a multiple of 8 up to 4096 and groups <= 32 dividing C "
-                             f"(got B {b}, HW {hw}, C {c}, groups {groups})")
-        return n
+        return self._scratch_numel(self.lib.dadd_groupnorm_grad_ws_floats, (b, hw, c, groups),
+                                   "groupnorm_grad takes C a multiple of 8 up to 4096 and groups <= 32 dividing C "
+                                   "(got B {}, HW {}, C {}, groups {})")
 
     def groupnorm_grad(self, x1, x2, dy, gamma, beta, *, dx1=None, dx2=None, dgamma=None, dbeta=None, ws, groups, eps,
                        silu):
@@ -488,12 +510,14 @@ class HipBackend:
         assert dy.shape == x1.shape[:-1] + (c,) and (x2 is None or x2.shape[:-1] == x1.shape[:-1])
         assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == c \
             and gamma.is_contiguous() and beta.is_contiguous()
-        assert (dgamma is None) == (dbeta is None) and (dx1 is not None or dgamma is not None)
-        assert dgamma is None or (dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c
-                                  and dgamma.is_contiguous() and dbeta.is_contiguous())
+        # (the asserts keep the parent's order - together / shaped / dx shapes / ws - so a call that breaks several rules
+        # fails on the same one, with the same message, as before the checks were shared)
+        together, shaped, ws_ok = self._param_grad_checks(dgamma, dbeta, c, ws, need)
+        assert together and (dx1 is not None or dgamma is not None)
+        assert shaped
         assert (dx1 is None or dx1.shape == x1.shape) and ((dx2 is not None) == (dx1 is not None and x2 is not None)) \
             and (dx2 is None or dx2.shape == x2.shape)
-        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, (ws.shape, need)
+        assert ws_ok, (ws.shape, need)
         d = self._gdesc
         d.x1, d.x2, d.dy, d.gamma, d.beta = _p(x1), _p(x2), _p(dy), _p(gamma), _p(beta)
         d.dx1, d.dx2, d.dgamma, d.dbeta, d.ws = _p(dx1), _p(dx2), _p(dgamma), _p(dbeta), _p(ws)
@@ -502,10 +526,8 @@ class HipBackend:
 
     def layernorm_grad_ws_numel(self, m, c):
         """fp32 elements of the ``ws`` scratch of ``layernorm_grad``: per-workgroup column sums [nblk][C][2]."""
-        n = int(self.lib.dadd_layernorm_grad_ws_floats(m, c))
-        if n < 0:
-            raise ValueError(f"layernorm_grad takes C a multiple of 8 up to 2048 and at least one row (got M {m}, C {c})")
-        return n
+        return self._scratch_numel(self.lib.dadd_layernorm_grad_ws_floats, (m, c),
+                                   "layernorm_grad takes C a multiple of 8 up to 2048 and at least one row (got M {}, C {})")
 
     def layernorm_grad(self, x, dy, gamma, *, dx=None, dgamma=None, dbeta=None, ws=None, eps=1e-5):
         """Backward of ``layernorm`` over the last axis: from the forward's input x [..., C] and dy of the same shape (fp16
@@ -520,11 +542,11 @@ class HipBackend:
         for t in (x, dy, dx):
             assert t is None or (t.is_contiguous() and t.dtype in _SFX and t.shape == x.shape), "x, dy, dx: one 16-bit shape"
         assert gamma.dtype == torch.float32 and gamma.numel() == c and gamma.is_contiguous()
-        assert (dgamma is None) == (dbeta is None) and (dx is not None or dgamma is not None)
-        if dgamma is not None:
-            assert dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c \
-                and dgamma.is_contiguous() and dbeta.is_contiguous()
-            assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        # (same order as groupnorm_grad; ws is asked for only with the parameter gradients, and its message is ``need``)
+        together, shaped, ws_ok = self._param_grad_checks(dgamma, dbeta, c, ws, need)
+        assert together and (dx is not None or dgamma is not None)
+        assert shaped
+        assert dgamma is None or ws_ok, need
         L.check(fn(_p(x), _p(dy), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), _p(ws), m, c, float(eps), self.s))
 
     def geglu(self, h, y):
@@ -533,8 +555,7 @@ class HipBackend:
         training step keeps h for ``geglu_grad``; the inference plans keep the GEMM epilogue."""
         f = y.shape[-1]
         fn = getattr(self.lib, "dadd_geglu_" + _sfx(h, y))
-        if f % 8 or f == 0:
-            raise ValueError(f"geglu: F = {f} must be a positive multiple of 8")
+        self._pointwise_width("geglu", f)
         assert h.shape == y.shape[:-1] + (2 * f,) and h.is_contiguous() and y.is_contiguous() and h.dtype in _SFX
         L.check(fn(_p(h), _p(y), h.numel() // (2 * f), f, self.s))
 
@@ -543,8 +564,7 @@ class HipBackend:
         same erf approximation as the forward.  h and dh [..., 2F], dy [..., F], all fp16 or all bf16."""
         f = dy.shape[-1]
         fn = getattr(self.lib, "dadd_geglu_grad_" + _sfx(h, dy, dh))
-        if f % 8 or f == 0:
-            raise ValueError(f"geglu_grad: F = {f} must be a positive multiple of 8")
+        self._pointwise_width("geglu_grad", f)
         assert h.shape == dy.shape[:-1] + (2 * f,) and dh.shape == h.shape and h.dtype in _SFX
         assert h.is_contiguous() and dy.is_contiguous() and dh.is_contiguous()
         L.check(fn(_p(h), _p(dy), _p(dh), h.numel() // (2 * f), f, self.s))
@@ -556,8 +576,7 @@ class HipBackend:
         keep the GEMM epilogue."""
         f = x.shape[-1]
         fn = getattr(self.lib, "dadd_gelu_" + _sfx(x, y))
-        if f % 8 or f == 0:
-            raise ValueError(f"gelu: F = {f} must be a positive multiple of 8")
+        self._pointwise_width("gelu", f)
         assert y.shape == x.shape and x.is_contiguous() and y.is_contiguous() and x.dtype in _SFX
         L.check(fn(_p(x), _p(y), x.numel() // f, f, self.s))
 
@@ -566,8 +585,7 @@ class HipBackend:
         x, dy and dx [..., F], all fp16 or all bf16."""
         f = x.shape[-1]
         fn = getattr(self.lib, "dadd_gelu_grad_" + _sfx(x, dy, dx))
-        if f % 8 or f == 0:
-            raise ValueError(f"gelu_grad: F = {f} must be a positive multiple of 8")
+        self._pointwise_width("gelu_grad", f)
         assert dy.shape == x.shape and dx.shape == x.shape and x.dtype in _SFX
         assert x.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
         L.check(fn(_p(x), _p(dy), _p(dx), x.numel() // f, f, self.s))
@@ -586,10 +604,8 @@ class HipBackend:
 
     def purifier_gate_tail_grad_ws_numel(self, m, c):
         """fp32 elements of the ``ws`` scratch of ``purifier_gate_tail_grad``: per-workgroup column sums [nblk][C][2]."""
-        n = int(self.lib.dadd_purifier_gate_tail_grad_ws_floats(m, c))
-        if n < 0:
-            raise ValueError(f"purifier_gate_tail_grad takes C a multiple of 8 up to 2048 and at least one row (got M {m}, C {c})")
-        return n
+        return self._scratch_numel(self.lib.dadd_purifier_gate_tail_grad_ws_floats, (m, c),
+                                   "purifier_gate_tail_grad takes C a multiple of 8 up to 2048 and at least one row (got M {}, C {})")
 
     def purifier_gate_tail_grad(self, img, dis, z, dout, gamma, *, dimg=None, ddis=None, dz=None, dgamma=None, dbeta=None,
                                 ws=None, eps=1e-5):
@@ -607,14 +623,14 @@ class HipBackend:
             assert t is None or (t.is_contiguous() and t.dtype in _SFX and t.shape == img.shape), "one 16-bit shape"
         assert dout.dtype == torch.float32 and dout.shape == img.shape and dout.is_contiguous()
         assert gamma.dtype == torch.float32 and gamma.numel() == c and gamma.is_contiguous()
-        if (dgamma is None) != (dbeta is None):
+        # (the two ValueErrors come before the asserts, as they always did: "come together" wins over "no output")
+        together, shaped, ws_ok = self._param_grad_checks(dgamma, dbeta, c, ws, need)
+        if not together:
             raise ValueError("purifier_gate_tail_grad: dgamma and dbeta come together")
         if dimg is None and ddis is None and dz is None and dgamma is None:
             raise ValueError("purifier_gate_tail_grad: no output")
-        if dgamma is not None:
-            assert dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.numel() == dbeta.numel() == c \
-                and dgamma.is_contiguous() and dbeta.is_contiguous()
-            assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need, need
+        assert shaped
+        assert dgamma is None or ws_ok, need
         L.check(fn(_p(img), _p(dis), _p(z), _p(dout), _p(gamma), _p(dimg), _p(ddis), _p(dz), _p(dgamma), _p(dbeta), _p(ws),
                    m, c, float(eps), self.s))
 
@@ -622,10 +638,8 @@ class HipBackend:
     def linear_rows_grad_ws_numel(self, m, k, n):
         """fp32 elements of the ``ws`` scratch of ``linear_rows_grad`` with ``dx``: the per-strip partial sums
         [strips][M][K]."""
-        nw = int(self.lib.dadd_linear_rows_grad_ws_floats(m, k, n))
-        if nw < 0:
-            raise ValueError(f"linear_rows_grad takes K a multiple of 8 up to 2048 and M, N >= 1 (got M {m}, K {k}, N {n})")
-        return nw
+        return self._scratch_numel(self.lib.dadd_linear_rows_grad_ws_floats, (m, k, n),
+                                   "linear_rows_grad takes K a multiple of 8 up to 2048 and M, N >= 1 (got M {}, K {}, N {})")
 
     def linear_rows_grad(self, x, w, dy, *, dx=None, dw=None, db=None, ws=None, act_in=0):
         """Backward of ``linear_rows(x, w, bias, out, act_in, 0)``: from the forward's fp32 input x [M][K] (the
@@ -667,10 +681,8 @@ class HipBackend:
 
     def rowvec_grad_ws_numel(self, b, hw, c):
         """fp32 elements of the ``ws`` scratch of ``rowvec_grad``: the column sums of every 64-pixel chunk."""
-        nw = int(self.lib.dadd_rowvec_grad_ws_floats(b, hw, c))
-        if nw < 0:
-            raise ValueError(f"rowvec_grad takes C a multiple of 8, B in 1..65535 and HW >= 1 (got B {b}, HW {hw}, C {c})")
-        return nw
+        return self._scratch_numel(self.lib.dadd_rowvec_grad_ws_floats, (b, hw, c),
+                                   "rowvec_grad takes C a multiple of 8, B in 1..65535 and HW >= 1 (got B {}, HW {}, C {})")
 
     def rowvec_grad(self, dy, drow, ws=None):
         """Gradient of the row ``EPI_ROWVEC`` adds: drow[b][c] = sum over the pixels of dy [B, ..., C] (fp16 or bf16, NHWC)
@@ -688,10 +700,8 @@ class HipBackend:
     # -- training backward of attention (csrc/attn_grad.hip)
     def attn_grad_ws_numel(self, b, heads, nq):
         """fp32 elements of the ``ws`` scratch of an ``attn_grad`` call: (LSE, D) per (sample, head, query row)."""
-        n = int(self.lib.dadd_attn_grad_ws_floats(b, heads, nq))
-        if n < 0:
-            raise ValueError(f"attn_grad takes positive sizes (got B {b}, heads {heads}, Nq {nq})")
-        return n
+        return self._scratch_numel(self.lib.dadd_attn_grad_ws_floats, (b, heads, nq),
+                                   "attn_grad takes positive sizes (got B {}, heads {}, Nq {})")
 
     @staticmethod
     def _token_ld(t, what):

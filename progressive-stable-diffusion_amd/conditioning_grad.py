@@ -117,10 +117,9 @@ def time_embedding(be, params, t, proj_keys, dim=320, prefix="unet.unet.time_emb
     gradient of the concatenation)."""
     f16 = torch.float16
     t = t.reshape(-1).to(torch.int64).contiguous()
-    be.wait_current()
-    feat = be.empty((t.shape[0], dim), torch.float32)
-    be.timestep_features(t, feat)
-    be.release_to_current()
+    with G.on_backend(be):
+        feat = be.empty((t.shape[0], dim), torch.float32)
+        be.timestep_features(t, feat)
     h = G.linear_rows(be, feat, params[prefix + ".linear_1.weight"], params[prefix + ".linear_1.bias"], weight_dtype=f16)
     h = G.linear_rows(be, h, params[prefix + ".linear_2.weight"], params[prefix + ".linear_2.bias"], act_in=1, weight_dtype=f16)
     w = torch.cat([params[k + ".weight"] for k in proj_keys])

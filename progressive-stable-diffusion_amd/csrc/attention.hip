@@ -25,23 +25,6 @@ constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
 // V row stride (halfs) such that 8 consecutive rows x 32 B hit distinct banks for the tr reads.
 constexpr int v_stride(int dvp) { return ((dvp * 2) % 64 == 32) ? dvp : dvp + 16; }
 
-__device__ __forceinline__ h8 tr_pair(const half_t* lds_row_lo, const half_t* lds_row_hi) {
-#ifdef DADD_BF16
-  typedef __attribute__((address_space(3))) h4 lds_v4;
-  const h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_lo);
-  const h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_hi);
-  return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#else
-  typedef __attribute__((address_space(3))) fp16x4 lds_v4;
-  const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_lo);
-  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_hi);
-  h8 r;
-  r[0] = (half_t)a[0]; r[1] = (half_t)a[1]; r[2] = (half_t)a[2]; r[3] = (half_t)a[3];
-  r[4] = (half_t)b[0]; r[5] = (half_t)b[1]; r[6] = (half_t)b[2]; r[7] = (half_t)b[3];
-  return r;
-#endif
-}
-
 __device__ __forceinline__ h8 pack_p(const f4& lo, const f4& hi) {
   h8 r;
 #pragma unroll
@@ -374,7 +357,7 @@ __global__ __launch_bounds__(NW * 64, DR <= 96 ? 2 : 1) void flash_kernel(const 
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const half_t* base = Vc + va_off + kb * 32 * VLD + df * 16;
-        const h8 va = tr_pair(base, base + 16 * VLD);
+        const h8 va = dadd_tr_pair(base, base + 16 * VLD);
 #pragma unroll
         for (int f = 0; f < QF; ++f)
           oacc[df][f] = DADD_MFMA_16X16X32(va, pb[f][kb], oacc[df][f], 0, 0, 0);
@@ -530,7 +513,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(const XattnArgs p) {
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       const half_t* base = Vs + (kb * 32 + 4 * g + (li >> 2)) * VLD + df * 16 + 4 * (li & 3);
-      vA[df][kb] = tr_pair(base, base + 16 * VLD);
+      vA[df][kb] = dadd_tr_pair(base, base + 16 * VLD);
     }
 
   const size_t tok0 = (size_t)b * p.N;

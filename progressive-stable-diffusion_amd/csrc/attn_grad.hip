@@ -91,23 +91,6 @@ struct AttnGradArgs {
   float do_scale, scale_log2, inv_sqrt_d;
 };
 
-__device__ __forceinline__ h8 ag_tr_pair(const half_t* lds_row_lo, const half_t* lds_row_hi) {
-#ifdef DADD_BF16
-  typedef __attribute__((address_space(3))) h4 lds_v4;
-  const h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_lo);
-  const h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_hi);
-  return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#else
-  typedef __attribute__((address_space(3))) fp16x4 lds_v4;
-  const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_lo);
-  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_hi);
-  h8 r;
-  r[0] = (half_t)a[0]; r[1] = (half_t)a[1]; r[2] = (half_t)a[2]; r[3] = (half_t)a[3];
-  r[4] = (half_t)b[0]; r[5] = (half_t)b[1]; r[6] = (half_t)b[2]; r[7] = (half_t)b[3];
-  return r;
-#endif
-}
-
 __device__ __forceinline__ h8 ag_pack(const f4& lo, const f4& hi) {   // the rounding of P / dS to the storage type
   h8 r;
 #pragma unroll
@@ -177,7 +160,7 @@ __device__ __forceinline__ void ag_tr_accum(f4 (&acc)[AgGeom<DR>::DF], const hal
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       const half_t* base = tr + kb * 32 * LD + df * 16;
-      const h8 a = ag_tr_pair(base, base + 16 * LD);
+      const h8 a = dadd_tr_pair(base, base + 16 * LD);
       acc[df] = DADD_MFMA_16X16X32(a, pb[kb], acc[df], 0, 0, 0);
     }
   }

@@ -29,7 +29,6 @@
 #define gn_grad_stats_kernel gn_grad_stats_kernel_bf16
 #define gn_grad_partial_kernel gn_grad_partial_kernel_bf16
 #define gn_grad_apply_kernel gn_grad_apply_kernel_bf16
-#define norm_grad_finish_kernel norm_grad_finish_kernel_bf16
 #define layernorm_grad_kernel layernorm_grad_kernel_bf16
 #define geglu_kernel geglu_kernel_bf16
 #define geglu_grad_kernel geglu_grad_kernel_bf16
@@ -44,7 +43,6 @@
 #define gelu_grad_kernel gelu_grad_kernel_bf16
 #define gate_tail_kernel gate_tail_kernel_bf16
 #define gate_tail_grad_kernel gate_tail_grad_kernel_bf16
-#define gate_tail_finish_kernel gate_tail_finish_kernel_bf16
 #define rowvec_grad_kernel rowvec_grad_kernel_bf16
 #define rowvec_grad_finish_kernel rowvec_grad_finish_kernel_bf16
 #define relayout_kernel relayout_kernel_bf16

@@ -44,7 +44,6 @@ __global__ __launch_bounds__(256) void gelu_grad_kernel(const half_t* __restrict
 // two-pass) and xhat = d * rstd.  A row that sits at 50 with a spread of 0.1 keeps xhat to fp32 accuracy of the spread,
 // not of the mean: the fp32 output (absolute 2e-5) and dgamma ((M + 16) 2^-24 sum |dout xhat|) both need that.
 constexpr int GT_MAXV = 4;       // C <= 2048
-constexpr int GT_MAX_BLOCKS = 256;
 
 __device__ __forceinline__ float gt_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
 
@@ -91,15 +90,6 @@ __device__ __forceinline__ void gt_row(const half_t* __restrict__ img, const hal
   rstd = rsqrtf(wave_sum(sq) * invc + eps);
 }
 
-__device__ __forceinline__ void gt_load8(const float* __restrict__ p, float (&v)[8]) {
-  const f4 a = *reinterpret_cast<const f4*>(p), b = *reinterpret_cast<const f4*>(p + 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[e] = a[e];
-    v[e + 4] = b[e];
-  }
-}
-
 __global__ __launch_bounds__(256) void gate_tail_kernel(const half_t* __restrict__ img, const half_t* __restrict__ dis,
                                                         const half_t* __restrict__ z, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float* __restrict__ out, int M,
@@ -116,8 +106,8 @@ __global__ __launch_bounds__(256) void gate_tail_kernel(const half_t* __restrict
     const int i = lane + 64 * u;
     if (i < nvec) {
       float gm[8], bt[8];
-      gt_load8(gamma + i * 8, gm);
-      gt_load8(beta + i * 8, bt);
+      dadd_load8(gamma + i * 8, gm);
+      dadd_load8(beta + i * 8, bt);
       f4 o0, o1;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -133,7 +123,8 @@ __global__ __launch_bounds__(256) void gate_tail_kernel(const half_t* __restrict
 
 // Backward: the grid is bounded and every wave strides over rows, keeping the column sums of dout and dout * xhat of its
 // rows in registers (layernorm_grad_kernel's scheme).  The four waves of a block add theirs in wave order through LDS; the
-// block writes part[block][C][2].  dimg / ddis / dz may each be NULL; part NULL: no parameter gradients.
+// block writes part[block][C][2], which dadd_norm_grad_finish (norm_grad.hip) sums into dgamma / dbeta.  dimg / ddis / dz
+// may each be NULL; part NULL: no parameter gradients.
 __global__ __launch_bounds__(256) void gate_tail_grad_kernel(const half_t* __restrict__ img, const half_t* __restrict__ dis,
                                                              const half_t* __restrict__ z, const float* __restrict__ dout,
                                                              const float* __restrict__ gamma, half_t* __restrict__ dimg,
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(256) void gate_tail_grad_kernel(const half_t* __res
     const int i = lane + 64 * u;
 #pragma unroll
     for (int e = 0; e < 8; ++e) gm[u][e] = sb[u][e] = sg[u][e] = 0.f;
-    if (i < nvec) gt_load8(gamma + i * 8, gm[u]);
+    if (i < nvec) dadd_load8(gamma + i * 8, gm[u]);
   }
   for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
     float d[GT_MAXV][8], go[GT_MAXV][8], rstd;
@@ -158,7 +149,7 @@ __global__ __launch_bounds__(256) void gate_tail_grad_kernel(const half_t* __res
 #pragma unroll
     for (int u = 0; u < GT_MAXV; ++u) {
       const int i = lane + 64 * u;
-      if (i < nvec) gt_load8(dout + (size_t)row * C + i * 8, go[u]);
+      if (i < nvec) dadd_load8(dout + (size_t)row * C + i * 8, go[u]);
     }
     gt_row(img, dis, z, (size_t)row, C, lane, eps, d, dv, zv, rstd);
     float s1 = 0.f, s2 = 0.f;
@@ -223,43 +214,6 @@ __global__ __launch_bounds__(256) void gate_tail_grad_kernel(const half_t* __res
   for (int k = threadIdx.x; k < 2 * C; k += 256) o[k] = sm[k];
 }
 
-// Column sums of part [nterm][C][2] -> dbeta (element 0) and dgamma (element 1), overwritten: norm_grad_finish_kernel's
-// order.  A block takes 32 channels; thread (q, channel) adds the terms q, q + 8, ... in double, the eight slices are then
-// added in slice order.
-__global__ __launch_bounds__(256) void gate_tail_finish_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta, int nterm, int C) {
-  __shared__ double red[8][32][2];
-  const int t = threadIdx.x, ch = t & 31, q = t >> 5;
-  const int c = blockIdx.x * 32 + ch;
-  double a = 0.0, d = 0.0;
-  if (c < C) {
-    for (int k = q; k < nterm; k += 8) {
-      const float2 v = *reinterpret_cast<const float2*>(part + ((size_t)k * C + c) * 2);
-      a += (double)v.x;
-      d += (double)v.y;
-    }
-  }
-  red[q][ch][0] = a;
-  red[q][ch][1] = d;
-  __syncthreads();
-  if (t < 32 && c < C) {
-    a = red[0][ch][0];
-    d = red[0][ch][1];
-#pragma unroll
-    for (int s = 1; s < 8; ++s) {
-      a += red[s][ch][0];
-      d += red[s][ch][1];
-    }
-    dbeta[c] = (float)a;
-    dgamma[c] = (float)d;
-  }
-}
-
-int gt_blocks(int M) {
-  const int n = (M + 7) / 8;       // two rows per wave before the grid stops growing
-  return n < GT_MAX_BLOCKS ? n : GT_MAX_BLOCKS;
-}
-
 bool gt_sizes_ok(int M, int C) { return M > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * GT_MAXV; }
 
 }  // namespace
@@ -268,7 +222,7 @@ bool gt_sizes_ok(int M, int C) { return M > 0 && C > 0 && C % 8 == 0 && C <= 8 *
 // host only, one copy for both storage types
 extern "C" long long dadd_purifier_gate_tail_grad_ws_floats(int M, int C) {
   if (!gt_sizes_ok(M, C)) return -1;
-  return (long long)gt_blocks(M) * C * 2;
+  return (long long)dadd_row_wave_blocks(M) * C * 2;
 }
 #endif
 
@@ -324,7 +278,7 @@ extern "C" int dadd_purifier_gate_tail_grad_f16(const void* img, const void* dis
                    dadd_aligned16(gamma) && dadd_aligned16(dimg) && dadd_aligned16(ddis) && dadd_aligned16(dz) &&
                    (((uintptr_t)ws) & 7) == 0, "purifier_gate_tail_grad: pointers must be 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nblk = gt_blocks(M);
+  const int nblk = dadd_row_wave_blocks(M);
   float* part = dgamma ? ws : nullptr;
   const int nout = (dimg != nullptr) + (ddis != nullptr) + (dz != nullptr);
   dadd_launch({DADD_KNAME("gate_tail_grad_kernel"), 0.0, (double)M * C * (10.0 + 2.0 * nout)}, gate_tail_grad_kernel, dim3(nblk),
@@ -332,10 +286,5 @@ extern "C" int dadd_purifier_gate_tail_grad_f16(const void* img, const void* dis
               static_cast<const half_t*>(dis), static_cast<const half_t*>(z), dout, gamma, static_cast<half_t*>(dimg),
               static_cast<half_t*>(ddis), static_cast<half_t*>(dz), part, M, C, eps);
   DADD_LAUNCH_CHECK();
-  if (dgamma) {
-    dadd_launch({DADD_KNAME("gate_tail_finish_kernel"), 0.0, (double)nblk * C * 8.0}, gate_tail_finish_kernel,
-                dim3((C + 31) / 32), dim3(256), 0, s, (const float*)ws, dgamma, dbeta, nblk, C);
-    DADD_LAUNCH_CHECK();
-  }
-  return DADD_OK;
+  return dgamma ? dadd_norm_grad_finish(ws, dgamma, dbeta, nblk, C, s) : DADD_OK;
 }

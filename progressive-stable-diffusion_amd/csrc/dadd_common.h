@@ -80,6 +80,19 @@ inline void dadd_launch(const DaddLaunchTag& tag, void (*kernel)(KA...), dim3 gr
     hipLaunchKernelGGL(kernel, grid, block, smem, s, static_cast<KA>(args)...);
 }
 
+// ---- row-wave backward kernels: grid size and the column-sum finish (norm_grad.hip) --------------------------------
+// Grid of a kernel whose waves stride over rows (layernorm_grad_kernel, gate_tail_grad_kernel): four waves per block, two
+// rows per wave before the grid stops growing at 256 blocks.  It is also the number of partials [C][2] the kernel writes.
+static inline int dadd_row_wave_blocks(int M) {
+  const int n = (M + 7) / 8;
+  return n < 256 ? n : 256;
+}
+// Launches norm_grad_finish_kernel: column sums of part [nterm][C][2] -> dbeta (element 0) and dgamma (element 1),
+// overwritten.  One fp32 kernel, compiled in the fp16 translation unit of norm_grad.hip and shared by both storage types.
+// Internal to the library: hidden, so that the dynamic symbol table stays what the headers under include/ declare.
+__attribute__((visibility("hidden"))) int dadd_norm_grad_finish(const float* part, float* dgamma, float* dbeta,
+                                                                int nterm, int C, hipStream_t s);
+
 // ---- device helpers -------------------------------------------------------------------------
 // c + a[0] * b[0] + a[1] * b[1] in one v_dot2 (exact 16-bit products, fp32 sum) on the storage type
 __device__ __forceinline__ float dadd_fdot2(h2 a, h2 b, float c) {
@@ -158,6 +171,43 @@ __device__ __forceinline__ float dadd_max_x16x32(float v) {
   v = fmaxf(a, b);
   dadd_pair32(v, a, b);
   return fmaxf(a, b);
+}
+// Transposed LDS read of an MFMA operand: two ds_read_b64_tr_b16, 16 rows apart.  Lane (g, li) gets the eight values
+// rows 4g..4g+3 of lds_row_lo and of lds_row_hi, column li (the lane map is derived in wgrad.hip's header comment).
+// The read gathers across lanes: EXEC must be all ones.
+__device__ __forceinline__ h8 dadd_tr_pair(const half_t* lds_row_lo, const half_t* lds_row_hi) {
+#ifdef DADD_BF16
+  typedef __attribute__((address_space(3))) h4 lds_v4;
+  const h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_lo);
+  const h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_hi);
+  return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+#else
+  typedef __attribute__((address_space(3))) fp16x4 lds_v4;
+  const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_lo);
+  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_hi);
+  h8 r;
+  r[0] = (half_t)a[0]; r[1] = (half_t)a[1]; r[2] = (half_t)a[2]; r[3] = (half_t)a[3];
+  r[4] = (half_t)b[0]; r[5] = (half_t)b[1]; r[6] = (half_t)b[2]; r[7] = (half_t)b[3];
+  return r;
+#endif
+}
+// Eight consecutive elements as fp32 registers: one 16-byte load of the storage type, two of fp32; and the fp32 store
+__device__ __forceinline__ void dadd_load8(const half_t* p, float (&o)[8]) {
+  const h8 v = *reinterpret_cast<const h8*>(p);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) o[c] = (float)v[c];
+}
+__device__ __forceinline__ void dadd_load8(const float* p, float (&o)[8]) {
+  const f4 a = *reinterpret_cast<const f4*>(p), b = *reinterpret_cast<const f4*>(p + 4);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    o[c] = a[c];
+    o[c + 4] = b[c];
+  }
+}
+__device__ __forceinline__ void dadd_store8(float* p, const float (&v)[8]) {
+  *reinterpret_cast<f4*>(p) = f4{v[0], v[1], v[2], v[3]};
+  *reinterpret_cast<f4*>(p + 4) = f4{v[4], v[5], v[6], v[7]};
 }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -48,24 +48,6 @@ struct EndWgradArgs {
   long long ndw, slab;    // fp32 elements of dw, and of one slab (dw + the bias sums, padded to a multiple of 4)
 };
 
-// two ds_read_b64_tr_b16, 16 rows apart (wgrad.hip's wg_tr_pair)
-__device__ __forceinline__ h8 eg_tr_pair(const half_t* lds_row_lo, const half_t* lds_row_hi) {
-#ifdef DADD_BF16
-  typedef __attribute__((address_space(3))) h4 lds_v4;
-  const h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_lo);
-  const h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_hi);
-  return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#else
-  typedef __attribute__((address_space(3))) fp16x4 lds_v4;
-  const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_lo);
-  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_hi);
-  h8 r;
-  r[0] = (half_t)a[0]; r[1] = (half_t)a[1]; r[2] = (half_t)a[2]; r[3] = (half_t)a[3];
-  r[4] = (half_t)b[0]; r[5] = (half_t)b[1]; r[6] = (half_t)b[2]; r[7] = (half_t)b[3];
-  return r;
-#endif
-}
-
 __global__ __launch_bounds__(256) void end_wgrad_kernel(const EndWgradArgs p) {
   __shared__ __attribute__((aligned(16))) half_t As[EG_BM * EG_LD];   // thin im2col tile [p][j]
   __shared__ __attribute__((aligned(16))) half_t Bs[EG_BM * EG_LD];   // wide tile [p][n]
@@ -173,11 +155,11 @@ __global__ __launch_bounds__(256) void end_wgrad_kernel(const EndWgradArgs p) {
 #pragma unroll
     for (int ks = 0; ks < EG_BM / 32; ++ks) {
       const half_t* pb = b_rd + ks * 32 * EG_LD;
-      const h8 bw = eg_tr_pair(pb, pb + 16 * EG_LD);
+      const h8 bw = dadd_tr_pair(pb, pb + 16 * EG_LD);
 #pragma unroll
       for (int f = 0; f < 3; ++f) {
         const half_t* pa = a_rd + ks * 32 * EG_LD + f * 16;
-        const h8 at = eg_tr_pair(pa, pa + 16 * EG_LD);
+        const h8 at = dadd_tr_pair(pa, pa + 16 * EG_LD);
         acc[f] = DADD_MFMA_16X16X32(at, bw, acc[f], 0, 0, 0);
       }
     }

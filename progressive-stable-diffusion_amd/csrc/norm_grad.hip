@@ -383,6 +383,9 @@ __global__ __launch_bounds__(256) void gn_grad_apply_kernel(const GnGradArgs p) 
 
 // Column sums of the partials part [nterm][C][2] -> dbeta (element 0) and dgamma (element 1), overwritten.  A block takes
 // 32 channels; thread (q, channel) adds the terms q, q + 8, ... in double, the eight slices are then added in slice order.
+// fp32 only: compiled once, in the fp16 translation unit, and launched by dadd_norm_grad_finish for both storage types and
+// for the purifier's gate tail (cond_grad.hip).
+#ifndef DADD_BF16
 __global__ __launch_bounds__(256) void norm_grad_finish_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta, int nterm, int C) {
   __shared__ double red[8][32][2];
@@ -411,12 +414,12 @@ __global__ __launch_bounds__(256) void norm_grad_finish_kernel(const float* __re
     dgamma[c] = (float)d;
   }
 }
+#endif
 
 // LayerNorm backward: one wave per row with the row in registers, as layernorm_kernel; the grid is bounded and every wave
 // strides over rows, keeping the column sums of dy and dy*xhat of its rows in registers.  The four waves of a block add
 // theirs in wave order through LDS; the block writes part[block][C][2].
 constexpr int LNG_MAXV = 4;       // C <= 8*64*4 = 2048
-constexpr int LNG_MAX_BLOCKS = 256;
 template <bool DX>
 __global__ __launch_bounds__(256) void layernorm_grad_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
                                                              const float* __restrict__ gamma, half_t* __restrict__ dx,
@@ -530,11 +533,6 @@ __global__ __launch_bounds__(256) void layernorm_grad_kernel(const half_t* __res
   for (int k = threadIdx.x; k < 2 * C; k += 256) out[k] = sm[k];
 }
 
-int lng_blocks(int M) {
-  const int n = (M + 7) / 8;       // two rows per wave before the grid stops growing
-  return n < LNG_MAX_BLOCKS ? n : LNG_MAX_BLOCKS;
-}
-
 // GEGLU, one thread per 8 outputs.  gelu and its derivative share the erf of dadd_gelu: dadd_gelu_phi (gelu_phi.h).
 __global__ __launch_bounds__(256) void geglu_kernel(const half_t* __restrict__ h, half_t* __restrict__ y, int M, int F) {
   const int fv = F >> 3;
@@ -594,19 +592,20 @@ int gng_launch(const GnGradArgs& p, const GnGradGeom& g, int B, bool want_dx, fl
                 (unsigned)sm3, s, p);
     DADD_LAUNCH_CHECK();
   }
-  if (dgamma) {
-    const int nterm = B * p.nchunk;
-    dadd_launch({DADD_KNAME("norm_grad_finish_kernel"), 0.0, (double)nterm * p.C * 8.0}, norm_grad_finish_kernel,
-                dim3((p.C + 31) / 32), dim3(256), 0, s, (const float*)p.cp, dgamma, dbeta, nterm, p.C);
-    DADD_LAUNCH_CHECK();
-  }
-  return DADD_OK;
+  return dgamma ? dadd_norm_grad_finish(p.cp, dgamma, dbeta, B * p.nchunk, p.C, s) : DADD_OK;
 }
 
 }  // namespace
 
 #ifndef DADD_BF16
 // host only, one copy for both storage types (the geometry does not depend on the type)
+int dadd_norm_grad_finish(const float* part, float* dgamma, float* dbeta, int nterm, int C, hipStream_t s) {
+  dadd_launch({"norm_grad_finish_kernel", 0.0, (double)nterm * C * 8.0}, norm_grad_finish_kernel, dim3((C + 31) / 32),
+              dim3(256), 0, s, part, dgamma, dbeta, nterm, C);
+  DADD_LAUNCH_CHECK();
+  return DADD_OK;
+}
+
 extern "C" long long dadd_groupnorm_grad_ws_floats(int B, int HW, int C, int groups) {
   if (!gng_sizes_ok(B, HW, C, groups)) return -1;
   const GnGradGeom g = gng_geom(B, HW, C);
@@ -615,7 +614,7 @@ extern "C" long long dadd_groupnorm_grad_ws_floats(int B, int HW, int C, int gro
 
 extern "C" long long dadd_layernorm_grad_ws_floats(int M, int C) {
   if (M <= 0 || C <= 0 || C % 8 != 0 || C > 8 * 64 * LNG_MAXV) return -1;
-  return (long long)lng_blocks(M) * C * 2;
+  return (long long)dadd_row_wave_blocks(M) * C * 2;
 }
 #endif
 
@@ -666,7 +665,7 @@ extern "C" int dadd_layernorm_grad_f16(const void* x, const void* dy, const floa
   DADD_REQUIRE(dadd_aligned16(x) && dadd_aligned16(dy) && dadd_aligned16(dx) && dadd_aligned16(gamma) &&
                    (((uintptr_t)ws) & 7) == 0, "layernorm_grad: pointers must be 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nblk = lng_blocks(M);
+  const int nblk = dadd_row_wave_blocks(M);
   float* part = dgamma ? ws : nullptr;
   const double bytes = (double)M * C * (dx ? 6.0 : 4.0);
   const unsigned smem = (unsigned)((size_t)2 * C * sizeof(float));
@@ -679,12 +678,7 @@ extern "C" int dadd_layernorm_grad_f16(const void* x, const void* dy, const floa
                 smem, s, static_cast<const half_t*>(x), static_cast<const half_t*>(dy), gamma, static_cast<half_t*>(dx),
                 part, M, C, eps);
   DADD_LAUNCH_CHECK();
-  if (dgamma) {
-    dadd_launch({DADD_KNAME("norm_grad_finish_kernel"), 0.0, (double)nblk * C * 8.0}, norm_grad_finish_kernel,
-                dim3((C + 31) / 32), dim3(256), 0, s, (const float*)ws, dgamma, dbeta, nblk, C);
-    DADD_LAUNCH_CHECK();
-  }
-  return DADD_OK;
+  return dgamma ? dadd_norm_grad_finish(ws, dgamma, dbeta, nblk, C, s) : DADD_OK;
 }
 
 extern "C" int dadd_geglu_f16(const void* h, void* y, int M, int F, void* stream) {

@@ -41,23 +41,6 @@ __device__ __forceinline__ float rg_act_grad(float xf, int act) {
   }
   return 1.0f;
 }
-__device__ __forceinline__ void rg_load8(const half_t* p, float (&o)[8]) {
-  const h8 v = *reinterpret_cast<const h8*>(p);
-#pragma unroll
-  for (int c = 0; c < 8; ++c) o[c] = (float)v[c];
-}
-__device__ __forceinline__ void rg_load8(const float* p, float (&o)[8]) {
-  const f4 a = *reinterpret_cast<const f4*>(p), b = *reinterpret_cast<const f4*>(p + 4);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    o[c] = a[c];
-    o[c + 4] = b[c];
-  }
-}
-__device__ __forceinline__ void rg_store8(float* p, const float (&v)[8]) {
-  *reinterpret_cast<f4*>(p) = f4{v[0], v[1], v[2], v[3]};
-  *reinterpret_cast<f4*>(p + 4) = f4{v[4], v[5], v[6], v[7]};
-}
 
 // DX: the partial sums of dx go to `part`; DW: dw (and db when not NULL) are written.  Without DX w is not read.
 template <typename WT, bool DX, bool DW>
@@ -84,7 +67,7 @@ __global__ __launch_bounds__(256) void rows_grad_kernel(const float* __restrict_
 #pragma unroll
       for (int c = 0; c < 8; ++c) a[r][c] = dxa[r][c] = 0.f;
       if (DW && active && r < mr) {
-        rg_load8(x + (size_t)(m0 + r) * K + k0, a[r]);
+        dadd_load8(x + (size_t)(m0 + r) * K + k0, a[r]);
 #pragma unroll
         for (int c = 0; c < 8; ++c) a[r][c] = rg_act(a[r][c], act_in);
       }
@@ -96,8 +79,8 @@ __global__ __launch_bounds__(256) void rows_grad_kernel(const float* __restrict_
       float wv[8], dwv[8], dyr[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c) wv[c] = dwv[c] = 0.f;
-      if (DX && active) rg_load8(w + (size_t)n * K + k0, wv);
-      rg_load8(dys + nl * RG_MP, dyr);
+      if (DX && active) dadd_load8(w + (size_t)n * K + k0, wv);
+      dadd_load8(dys + nl * RG_MP, dyr);
 #pragma unroll
       for (int r = 0; r < RG_MP; ++r) {
 #pragma unroll
@@ -110,11 +93,11 @@ __global__ __launch_bounds__(256) void rows_grad_kernel(const float* __restrict_
         float* o = dw + (size_t)n * K + k0;
         if (m0 > 0) {                  // this lane stored the sum of the earlier passes itself
           float prev[8];
-          rg_load8(o, prev);
+          dadd_load8(o, prev);
 #pragma unroll
           for (int c = 0; c < 8; ++c) dwv[c] += prev[c];
         }
-        rg_store8(o, dwv);
+        dadd_store8(o, dwv);
       }
       if (DW && db != nullptr && lead && lane == 0) {
         float s = dyr[0];
@@ -131,11 +114,11 @@ __global__ __launch_bounds__(256) void rows_grad_kernel(const float* __restrict_
             float* s = red + r * RG_KT + lane * 8;
             if (v > 0) {
               float prev[8];
-              rg_load8(s, prev);
+              dadd_load8(s, prev);
 #pragma unroll
               for (int c = 0; c < 8; ++c) dxa[r][c] += prev[c];
             }
-            rg_store8(s, dxa[r]);
+            dadd_store8(s, dxa[r]);
           }
         }
         __syncthreads();
@@ -143,8 +126,8 @@ __global__ __launch_bounds__(256) void rows_grad_kernel(const float* __restrict_
       if (active) {
         for (int r = wave; r < mr; r += 4) {
           float v8[8];
-          rg_load8(red + r * RG_KT + lane * 8, v8);
-          rg_store8(part + ((size_t)blockIdx.x * M + m0 + r) * K + k0, v8);
+          dadd_load8(red + r * RG_KT + lane * 8, v8);
+          dadd_store8(part + ((size_t)blockIdx.x * M + m0 + r) * K + k0, v8);
         }
       }
     }

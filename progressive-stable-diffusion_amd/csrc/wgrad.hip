@@ -45,24 +45,6 @@ struct WgradArgs {
   int splitm, nu, nnt;    // slices, 32-row steps of m, 64-row n tiles
 };
 
-// two ds_read_b64_tr_b16, 16 rows apart (same helper as attention.hip's tr_pair)
-__device__ __forceinline__ h8 wg_tr_pair(const half_t* lds_row_lo, const half_t* lds_row_hi) {
-#ifdef DADD_BF16
-  typedef __attribute__((address_space(3))) h4 lds_v4;
-  const h4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_lo);
-  const h4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)lds_row_hi);
-  return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#else
-  typedef __attribute__((address_space(3))) fp16x4 lds_v4;
-  const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_lo);
-  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v4*)lds_row_hi);
-  h8 r;
-  r[0] = (half_t)a[0]; r[1] = (half_t)a[1]; r[2] = (half_t)a[2]; r[3] = (half_t)a[3];
-  r[4] = (half_t)b[0]; r[5] = (half_t)b[1]; r[6] = (half_t)b[2]; r[7] = (half_t)b[3];
-  return r;
-#endif
-}
-
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
   __shared__ __attribute__((aligned(16))) half_t As[WG_BM * WG_LD];   // dy tile [m][n]
   __shared__ __attribute__((aligned(16))) half_t Bs[WG_BM * WG_LD];   // x tile  [m][c] of this block's tap
@@ -145,8 +127,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
       for (int i = 0; i < 2; ++i) {
         const half_t* pa = a_rd + ks * 32 * WG_LD + i * 16;
         const half_t* pb = b_rd + ks * 32 * WG_LD + i * 16;
-        a[i] = wg_tr_pair(pa, pa + 16 * WG_LD);
-        b[i] = wg_tr_pair(pb, pb + 16 * WG_LD);
+        a[i] = dadd_tr_pair(pa, pa + 16 * WG_LD);
+        b[i] = dadd_tr_pair(pb, pb + 16 * WG_LD);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)

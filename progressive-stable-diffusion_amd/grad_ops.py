@@ -1,48 +1,69 @@
-"""Differentiable Linear / conv3x3, GroupNorm(+SiLU), LayerNorm, GEGLU and attention (self, general and the triple-pathway
-cross-attention) on the HIP kernels: the operators of a training step and their gradients.
-
-Matrix products: forward is ``HipBackend.igemm``; the data gradient is the same kernel on ``dy`` with the weight re-laid
-by ``dgrad_weight``; the weight and bias gradients are the M-reduction GEMM of ``HipBackend.wgrad`` (csrc/wgrad.hip).
-The resampling convs (``downsample2d``: stride 2; ``upsample2d``: through a nearest 2x upsample) get their data gradient
-from the gather-GEMM of ``HipBackend.dgrad_resample`` (csrc/dgrad.hip): per parity class of input pixels only the taps
-that reach it, on the weight re-laid by ``dgrad_weight_stride2`` / ``dgrad_weight_ups``.
-Norms and gating: forward is ``HipBackend.groupnorm`` / ``layernorm`` / ``geglu``, backward the reduction kernels of
-csrc/norm_grad.hip (``groupnorm_grad`` / ``layernorm_grad`` / ``geglu_grad``), which recompute the statistics from the
-saved input.  Attention: forward is ``HipBackend.self_attn`` / ``attention`` / ``tri_xattn``, backward the three launches
-of csrc/attn_grad.hip (``attn_grad``: row statistics recomputed from q, k, v and dy, then dK / dV, then dQ); the
-triple-pathway gradient is composed from it, one call per pathway with the gate or lambda as the scale of dy.
-With these a ResnetBlock2D and a full BasicTransformerBlock (attn1, attn2, feed-forward) are differentiable end to end.
-The UNet's 4-channel ends and the loss: ``conv_in`` (fp32 NCHW latents -> 16-bit NHWC, ``HipBackend.conv_in_nchw``) and
-``conv_out`` (16-bit NHWC -> fp32 NCHW, ``HipBackend.conv_cout4``) get their weight and bias gradients from the thin
-M-reduction GEMM of ``HipBackend.end_wgrad`` (csrc/end_grad.hip); the data gradient of ``conv_out`` is the conv_in kernel
-on dy with the weight re-laid by ``dgrad_weight_cout4`` (``HipBackend.dgrad_cout4``); ``mse_rows`` is the row-mean squared
-error with ``HipBackend.mse_rows_grad`` behind it.  A gradient now reaches every kind of UNet parameter.
-The conditioning front-end: ``gelu`` (exact-form GELU as a layer that keeps its input) and ``purifier_gate_tail``
-(LayerNorm(img - sigmoid(z) * dis)) on csrc/cond_grad.hip; with attention at d = 96 and any key count they make the
-FeaturePurifier and the image projections differentiable (``conditioning_grad``).
-The fp32 row path: ``linear_rows`` (fp32 rows against an fp32 or fp16 weight with the activation on the input side: the
-AOE projector, the time-embedding MLP, the concatenated ``time_emb_proj`` layers) and ``aoe_interp`` (the AOE class table)
-on csrc/rows_grad.hip (``HipBackend.linear_rows_grad`` / ``aoe_interp_grad``); ``conv3x3(rowvec=)`` adds a resnet's time row
-in the conv's epilogue and returns its gradient (``HipBackend.rowvec_grad``).  With them every parameter the reference
-trains has a gradient on the kernels (``conditioning_grad.ordinal_embedder`` / ``time_embedding``).
-These are operators, not the training loop: ``unet_grad`` assembles the UNet from them and ``training.Trainer`` the step;
-still missing are attention with Nq not a multiple of 16 and head dims other than 40 / 80 / 96 / 160.  The
-matrix products take ``prepared=``: the 16-bit copy and the data-gradient layout of a weight that ``optim.DgradRelayout``
-keeps, instead of a cast and a torch re-layout per call.  The
-optimizer that consumes the gradients is ``optim.FusedAdamW`` over an ``optim.ParamArena``: a master weight may be an
-arena view (``w = arena.param(name)``, or a leaf attached with ``arena.attach``, whose ``.grad`` then accumulates in place
-in the arena's flat gradient buffer).
+"""The differentiable operators of a training step: ``torch.autograd.Function``s whose forward and backward are launches
+of the HIP kernels through a backend (``HipBackend``, or the reference backends of the test-suite).
 
 Operands: ``x`` is a 16-bit (fp16 or bf16) NHWC / token-major tensor on the backend's device, ``w`` the **fp32 master**
 weight in the library layout ``[N][taps*C]`` (``[Cout][ky][kx][Cin]`` flattened), ``bias`` / ``gamma`` / ``beta`` fp32.
 The forward of a product rounds the master to ``x.dtype`` once and keeps the rounded copy for the backward; gradients of
-``w``, ``bias``, ``gamma`` and ``beta`` come back in fp32, the gradient of ``x`` in ``x.dtype``.
+``w``, ``bias``, ``gamma`` and ``beta`` come back in fp32, the gradient of ``x`` in ``x.dtype``.  Every backward recomputes
+what it needs (statistics, softmax rows, gates) from the saved inputs, in a fixed summation order.
+
+Every operator allocates and launches inside ``on_backend(be)``, the bracket that orders the backend's stream after
+torch's current stream and back; what runs before the bracket (casts, re-layouts, ``contiguous()``) is torch work on the
+current stream.
+
+=========================================  ==================================  ==========================================
+operator                                   forward                             backward
+=========================================  ==================================  ==========================================
+``linear``, ``conv3x3``                    ``igemm``                           ``dgrad`` (the forward kernel on dy with
+                                                                               ``dgrad_weight``), ``wgrad``
+``conv3x3(rowvec=)``                       ``igemm`` + ``EPI_ROWVEC``          the same, and ``rowvec_grad``
+``downsample2d``, ``upsample2d``           ``igemm`` (stride 2 / upsampled)    ``dgrad_resample`` (``dgrad_weight_stride2``
+                                                                               / ``dgrad_weight_ups``), ``wgrad``
+``conv_in``, ``conv_out``                  ``conv_in_nchw``, ``conv_cout4``    ``end_wgrad``; ``dgrad_cout4``
+                                                                               (``dgrad_weight_cout4``) for conv_out
+``mse_rows``                               ``mse_rows``                        ``mse_rows_grad``
+``linear_rows``, ``aoe_interp``            the fp32 row path                   ``linear_rows_grad``, ``aoe_interp_grad``
+``group_norm``, ``layer_norm``             ``groupnorm``, ``layernorm``        ``groupnorm_grad``, ``layernorm_grad``
+``geglu``, ``gelu``                        ``geglu``, ``gelu``                 ``geglu_grad``, ``gelu_grad``
+``purifier_gate_tail``                     ``purifier_gate_tail``              ``purifier_gate_tail_grad``
+``self_attention``, ``attention``          ``self_attn``, ``attention``        ``attn_grad``
+``tri_cross_attention``                    ``tri_xattn``                       one ``attn_grad`` per pathway, the gate or
+                                                                               lambda as the scale of dy
+=========================================  ==================================  ==========================================
+
+The matrix products take ``prepared=``: the 16-bit copy and the data-gradient layout of a weight that
+``optim.DgradRelayout`` keeps, instead of a cast and a torch re-layout per call.  A master weight may be a view of an
+``optim.ParamArena``, whose ``.grad`` then accumulates in the arena's flat gradient buffer for ``optim.FusedAdamW``.
+
+These are operators, not the model: ``conditioning_grad`` builds the conditioning front-end and the time path from them,
+``unet_grad`` the UNet, ``training.Trainer`` the step.  Not covered: attention with Nq not a multiple of 16 or a head dim
+other than 40 / 80 / 96 / 160, and the data gradient of ``conv3x3(stride=2)`` / ``conv3x3(ups=True)`` under those names
+(``downsample2d`` / ``upsample2d`` have it); DESIGN.md §7.1.
 """
 from __future__ import annotations
 
 import torch
 
 from . import lib as L
+
+
+class on_backend:
+    """The stream bracket of every operator here, ``with on_backend(be):`` - inside it the backend's stream runs after what
+    torch's current stream has produced, and after it (also when the body raises) torch's current stream waits for the
+    backend's.  Everything that allocates or launches through ``be`` goes inside; leaving either end out is a cross-stream
+    race that no test would catch.  Uses ``be.wait_current()`` and ``be.release_to_current()`` alone, so any backend with
+    those two serves.  A plain class, not a ``contextlib`` generator: a step enters it a few thousand times, and this form
+    costs 0.2 us more than the two bare calls where the generator costs 1 us."""
+    __slots__ = ("be",)
+
+    def __init__(self, be):
+        self.be = be
+
+    def __enter__(self):
+        self.be.wait_current()
+
+    def __exit__(self, *exc):
+        self.be.release_to_current()
 
 
 def dgrad_weight(w16: torch.Tensor, taps: int) -> torch.Tensor:
@@ -138,15 +159,14 @@ def _forward(be, x, w, bias, taps, stride, ups, rowvec=None, w16=None):
         ho, wo = (2 * h, 2 * wd) if ups else ((h - 1) // stride + 1, (wd - 1) // stride + 1)
         x4 = x
         out_shape4 = out_shape = (b, ho, wo, n)
-    be.wait_current()
-    y = be.empty(out_shape4, x.dtype)
-    if rowvec is None:
-        be.igemm(x4, w16, y, bias=bias, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
-                 flags=L.EPI_BIAS if bias is not None else 0)
-    else:
-        be.igemm(x4, w16, y, bias=bias, rowvec=rowvec, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
-                 flags=(L.EPI_BIAS if bias is not None else 0) | L.EPI_ROWVEC)
-    be.release_to_current()
+    with on_backend(be):
+        y = be.empty(out_shape4, x.dtype)
+        if rowvec is None:
+            be.igemm(x4, w16, y, bias=bias, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
+                     flags=L.EPI_BIAS if bias is not None else 0)
+        else:
+            be.igemm(x4, w16, y, bias=bias, rowvec=rowvec, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
+                     flags=(L.EPI_BIAS if bias is not None else 0) | L.EPI_ROWVEC)
     return x4, w16, y.view(out_shape)
 
 
@@ -156,23 +176,22 @@ def _backward(be, x4, w16, dy, taps, stride, ups, need_dx, need_dw, need_db, wt=
     resample = stride != 1 or ups
     if need_dx and wt is None:                             # torch plumbing, current stream
         wt = dgrad_weight(w16, taps) if not resample else dgrad_weight_ups(w16) if ups else dgrad_weight_stride2(w16)
-    be.wait_current()
-    dx = dw = db = None
-    if need_dx:
-        dx = be.empty(tuple(x4.shape), x4.dtype)
-        if resample:
-            be.dgrad_resample(dy4, wt, dx, stride=stride, ups=int(ups))
-        else:
-            be.dgrad(dy4, wt, dx, taps=taps)
-    if need_dw or need_db:
-        m = dy4.shape[0] * dy4.shape[1] * dy4.shape[2]
-        dw = be.empty((n, taps * c), torch.float32)
-        db = be.empty((n,), torch.float32) if need_db else None
-        splitm = be.wgrad_splitm(m, n, c, taps)
-        partial = be.empty((be.wgrad_partial_numel(splitm, n, c, taps),), torch.float32) if splitm > 1 else None
-        be.wgrad(dy4, x4, dw, dbias=db, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
-                 splitm=splitm, partial=partial)
-    be.release_to_current()
+    with on_backend(be):
+        dx = dw = db = None
+        if need_dx:
+            dx = be.empty(tuple(x4.shape), x4.dtype)
+            if resample:
+                be.dgrad_resample(dy4, wt, dx, stride=stride, ups=int(ups))
+            else:
+                be.dgrad(dy4, wt, dx, taps=taps)
+        if need_dw or need_db:
+            m = dy4.shape[0] * dy4.shape[1] * dy4.shape[2]
+            dw = be.empty((n, taps * c), torch.float32)
+            db = be.empty((n,), torch.float32) if need_db else None
+            splitm = be.wgrad_splitm(m, n, c, taps)
+            partial = be.empty((be.wgrad_partial_numel(splitm, n, c, taps),), torch.float32) if splitm > 1 else None
+            be.wgrad(dy4, x4, dw, dbias=db, taps=taps, stride=stride, ups=int(ups), pad=1 if taps == 9 else 0,
+                     splitm=splitm, partial=partial)
     return dx, dw, db
 
 
@@ -225,10 +244,9 @@ class _ProductRowvec(torch.autograd.Function):
         if need_dx or need_dw or need_db:
             dx, dw, db = _backward(be, x4, w16, dy, 9, 1, False, need_dx, need_dw, need_db, wt=ctx.wt)
         if need_row:
-            be.wait_current()
-            drow = be.empty((dy.shape[0], dy.shape[-1]), torch.float32)
-            be.rowvec_grad(dy, drow)
-            be.release_to_current()
+            with on_backend(be):
+                drow = be.empty((dy.shape[0], dy.shape[-1]), torch.float32)
+                be.rowvec_grad(dy, drow)
         return (dx.view(ctx.x_shape) if need_dx else None, dw if need_dw else None, db, drow, None, None)
 
 
@@ -322,10 +340,9 @@ class _ConvIn(torch.autograd.Function):
         w16 = w.detach().reshape(n, 9, ct).to(dtype)
         w8[:, :, :ct] = w16
         bias = None if bias is None else bias.detach().contiguous()
-        be.wait_current()
-        y = be.empty((b, h, wd, n), dtype)
-        be.conv_in_nchw(x, w8, bias, y)
-        be.release_to_current()
+        with on_backend(be):
+            y = be.empty((b, h, wd, n), dtype)
+            be.conv_in_nchw(x, w8, bias, y)
         need_dx = bool(data_grad) and ctx.needs_input_grad[0]
         ctx.save_for_backward(x, w16 if need_dx else None)
         ctx.be, ctx.need_dx = be, need_dx
@@ -342,16 +359,15 @@ class _ConvIn(torch.autograd.Function):
         ct, n = x.shape[1], dy.shape[-1]
         dy = dy.contiguous()
         wt = w16.flip(1).permute(2, 1, 0).contiguous() if need_dx else None     # [Ct][8 - tap][N]: torch plumbing, tiny
-        be.wait_current()
-        dx = dw = db = None
-        if need_dx:                      # the conv_out kernel on dy with the flipped, transposed weight
-            dx = be.empty(tuple(x.shape), torch.float32)
-            be.conv_cout4(dy.to(w16.dtype), wt, None, dx, mode=0)
-        if need_dw or need_db:
-            dw8, db = _end_wgrad(be, x, dy, (n, 9, 8), n, L.END_WGRAD_IN, need_db)
-            with be.ctx():
-                dw = dw8[:, :, :ct].reshape(n, 9 * ct)
-        be.release_to_current()
+        with on_backend(be):
+            dx = dw = db = None
+            if need_dx:                      # the conv_out kernel on dy with the flipped, transposed weight
+                dx = be.empty(tuple(x.shape), torch.float32)
+                be.conv_cout4(dy.to(w16.dtype), wt, None, dx, mode=0)
+            if need_dw or need_db:
+                dw8, db = _end_wgrad(be, x, dy, (n, 9, 8), n, L.END_WGRAD_IN, need_db)
+                with be.ctx():
+                    dw = dw8[:, :, :ct].reshape(n, 9 * ct)
         return dx, dw if need_dw else None, db, None, None, None
 
 
@@ -376,10 +392,9 @@ class _ConvOut(torch.autograd.Function):
         else:
             w16 = w.detach().to(x.dtype).contiguous()   # [Co][9*C] is pack_conv_cout4's [Co][9][C]
         bias = None if bias is None else bias.detach().contiguous()
-        be.wait_current()
-        y = be.empty((b, co, h, wd), torch.float32)
-        be.conv_cout4(x, w16.view(co, 9, c), bias, y, mode=0)
-        be.release_to_current()
+        with on_backend(be):
+            y = be.empty((b, co, h, wd), torch.float32)
+            be.conv_cout4(x, w16.view(co, 9, c), bias, y, mode=0)
         ctx.save_for_backward(x, w16)
         ctx.be, ctx.wt = be, wt
         return y
@@ -396,15 +411,14 @@ class _ConvOut(torch.autograd.Function):
         wt = ctx.wt
         if need_dx and wt is None:
             wt = dgrad_weight_cout4(w16)                       # torch plumbing, current stream
-        be.wait_current()
-        dx = dw = db = None
-        if need_dx:
-            dx = be.empty(tuple(x.shape), x.dtype)
-            be.dgrad_cout4(dy, wt, dx)
-        if need_dw or need_db:
-            dw, db = _end_wgrad(be, dy, x, (co, 9, c), co, L.END_WGRAD_OUT, need_db)
-            dw = dw.view(co, 9 * c)
-        be.release_to_current()
+        with on_backend(be):
+            dx = dw = db = None
+            if need_dx:
+                dx = be.empty(tuple(x.shape), x.dtype)
+                be.dgrad_cout4(dy, wt, dx)
+            if need_dw or need_db:
+                dw, db = _end_wgrad(be, dy, x, (co, 9, c), co, L.END_WGRAD_OUT, need_db)
+                dw = dw.view(co, 9 * c)
         return dx, dw if need_dw else None, db, None, None
 
 
@@ -415,10 +429,9 @@ class _MseRows(torch.autograd.Function):
             raise ValueError(f"mse_rows takes fp32 pred and target of one shape [B, ...], got {tuple(pred.shape)} {pred.dtype} "
                              f"and {tuple(target.shape)} {target.dtype}")
         pred, target = pred.contiguous(), target.contiguous()
-        be.wait_current()
-        out = be.empty((pred.shape[0],), torch.float32)
-        be.mse_rows(pred, target, out)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty((pred.shape[0],), torch.float32)
+            be.mse_rows(pred, target, out)
         ctx.save_for_backward(pred, target)
         ctx.be = be
         return out
@@ -430,10 +443,9 @@ class _MseRows(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return None, None, None
         drow = drow.float().contiguous()
-        be.wait_current()
-        dpred = be.empty(tuple(pred.shape), torch.float32)
-        be.mse_rows_grad(pred, target, drow, dpred)
-        be.release_to_current()
+        with on_backend(be):
+            dpred = be.empty(tuple(pred.shape), torch.float32)
+            be.mse_rows_grad(pred, target, drow, dpred)
         return dpred, None, None
 
 
@@ -454,10 +466,9 @@ class _LinearRows(torch.autograd.Function):
         x = x.contiguous()
         wk = w.detach().to(weight_dtype).contiguous()     # rounded once (fp16) and kept for the backward
         bias = None if bias is None else bias.detach().contiguous()
-        be.wait_current()
-        out = be.empty((m, n), torch.float32)
-        be.linear_rows(x, wk, bias, out, act_in, 0)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty((m, n), torch.float32)
+            be.linear_rows(x, wk, bias, out, act_in, 0)
         ctx.save_for_backward(x, wk)
         ctx.be, ctx.act_in = be, act_in
         return out
@@ -471,13 +482,12 @@ class _LinearRows(torch.autograd.Function):
             return (None,) * 6
         (m, k), n = x.shape, wk.shape[0]
         dy = dy.float().contiguous()
-        be.wait_current()
-        dx = be.empty((m, k), torch.float32) if need_dx else None
-        dw = be.empty((n, k), torch.float32) if need_dw or need_db else None
-        db = be.empty((n,), torch.float32) if need_db else None
-        ws = be.empty((be.linear_rows_grad_ws_numel(m, k, n),), torch.float32) if need_dx else None
-        be.linear_rows_grad(x, wk, dy, dx=dx, dw=dw, db=db, ws=ws, act_in=ctx.act_in)
-        be.release_to_current()
+        with on_backend(be):
+            dx = be.empty((m, k), torch.float32) if need_dx else None
+            dw = be.empty((n, k), torch.float32) if need_dw or need_db else None
+            db = be.empty((n,), torch.float32) if need_db else None
+            ws = be.empty((be.linear_rows_grad_ws_numel(m, k, n),), torch.float32) if need_dx else None
+            be.linear_rows_grad(x, wk, dy, dx=dx, dw=dw, db=db, ws=ws, act_in=ctx.act_in)
         return dx, dw if need_dw else None, db, None, None, None
 
 
@@ -492,10 +502,9 @@ class _AoeInterp(torch.autograd.Function):
             raise ValueError(f"aoe_interp takes labels [B], got {tuple(labels.shape)}")
         labels = labels.detach().float().contiguous()
         base, deltas = base.detach().contiguous(), deltas.detach().contiguous()
-        be.wait_current()
-        out = be.empty((labels.shape[0], base.shape[0]), torch.float32)
-        be.aoe_interp(labels, base, deltas, out)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty((labels.shape[0], base.shape[0]), torch.float32)
+            be.aoe_interp(labels, base, deltas, out)
         ctx.save_for_backward(labels)
         ctx.be, ctx.classes = be, deltas.shape[0] + 1
         return out
@@ -509,10 +518,9 @@ class _AoeInterp(torch.autograd.Function):
             return (None,) * 4
         dout = dout.float().contiguous()
         d = dout.shape[1]
-        be.wait_current()
-        dbase, ddeltas = be.empty((d,), torch.float32), be.empty((ctx.classes - 1, d), torch.float32)
-        be.aoe_interp_grad(labels, dout, dbase, ddeltas)
-        be.release_to_current()
+        with on_backend(be):
+            dbase, ddeltas = be.empty((d,), torch.float32), be.empty((ctx.classes - 1, d), torch.float32)
+            be.aoe_interp_grad(labels, dout, dbase, ddeltas)
         return None, dbase if need_b else None, ddeltas if need_d else None, None
 
 
@@ -587,11 +595,10 @@ class _GroupNorm(torch.autograd.Function):
         x = x.contiguous()
         x2 = None if x2 is None else x2.contiguous()
         gamma, beta = gamma.contiguous(), beta.contiguous()
-        be.wait_current()
-        y = be.empty(x.shape[:-1] + (c,), x.dtype)
-        ws = be.empty((x.shape[0] * L.GN_MAX_CHUNKS * groups * 2,), torch.float32)
-        be.groupnorm(x, x2, gamma, beta, y, ws, groups, eps, silu)
-        be.release_to_current()
+        with on_backend(be):
+            y = be.empty(x.shape[:-1] + (c,), x.dtype)
+            ws = be.empty((x.shape[0] * L.GN_MAX_CHUNKS * groups * 2,), torch.float32)
+            be.groupnorm(x, x2, gamma, beta, y, ws, groups, eps, silu)
         ctx.save_for_backward(x, x2, gamma, beta)
         ctx.be, ctx.cfg = be, (groups, eps, silu)
         return y
@@ -606,15 +613,14 @@ class _GroupNorm(torch.autograd.Function):
             return (None,) * 8
         dy = dy.to(x.dtype).contiguous()
         b, hw, c = x.shape[0], x.shape[1] * x.shape[2], dy.shape[-1]
-        be.wait_current()
-        dx1 = be.empty(tuple(x.shape), x.dtype) if need_dx else None
-        dx2 = be.empty(tuple(x2.shape), x.dtype) if need_dx and x2 is not None else None
-        dg = be.empty((c,), torch.float32) if need_dp else None
-        db = be.empty((c,), torch.float32) if need_dp else None
-        ws = be.empty((be.groupnorm_grad_ws_numel(b, hw, c, groups),), torch.float32)
-        be.groupnorm_grad(x, x2, dy, gamma, beta, dx1=dx1, dx2=dx2, dgamma=dg, dbeta=db, ws=ws, groups=groups, eps=eps,
-                          silu=silu)
-        be.release_to_current()
+        with on_backend(be):
+            dx1 = be.empty(tuple(x.shape), x.dtype) if need_dx else None
+            dx2 = be.empty(tuple(x2.shape), x.dtype) if need_dx and x2 is not None else None
+            dg = be.empty((c,), torch.float32) if need_dp else None
+            db = be.empty((c,), torch.float32) if need_dp else None
+            ws = be.empty((be.groupnorm_grad_ws_numel(b, hw, c, groups),), torch.float32)
+            be.groupnorm_grad(x, x2, dy, gamma, beta, dx1=dx1, dx2=dx2, dgamma=dg, dbeta=db, ws=ws, groups=groups, eps=eps,
+                              silu=silu)
         return (dx1 if need_x else None, dx2 if need_x2 else None, dg if need_g else None, db if need_b else None,
                 None, None, None, None)
 
@@ -625,10 +631,9 @@ class _LayerNorm(torch.autograd.Function):
         _check16(x, "x")
         _check_affine(gamma, beta, x.shape[-1])
         x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
-        be.wait_current()
-        y = be.empty(tuple(x.shape), x.dtype)
-        be.layernorm(x, gamma, beta, y, eps)
-        be.release_to_current()
+        with on_backend(be):
+            y = be.empty(tuple(x.shape), x.dtype)
+            be.layernorm(x, gamma, beta, y, eps)
         ctx.save_for_backward(x, gamma)
         ctx.be, ctx.eps = be, eps
         return y
@@ -643,58 +648,31 @@ class _LayerNorm(torch.autograd.Function):
             return (None,) * 5
         dy = dy.to(x.dtype).contiguous()
         c = x.shape[-1]
-        be.wait_current()
-        dx = be.empty(tuple(x.shape), x.dtype) if need_x else None
-        dg = be.empty((c,), torch.float32) if need_dp else None
-        db = be.empty((c,), torch.float32) if need_dp else None
-        ws = be.empty((be.layernorm_grad_ws_numel(x.numel() // c, c),), torch.float32) if need_dp else None
-        be.layernorm_grad(x, dy, gamma, dx=dx, dgamma=dg, dbeta=db, ws=ws, eps=ctx.eps)
-        be.release_to_current()
+        with on_backend(be):
+            dx = be.empty(tuple(x.shape), x.dtype) if need_x else None
+            dg = be.empty((c,), torch.float32) if need_dp else None
+            db = be.empty((c,), torch.float32) if need_dp else None
+            ws = be.empty((be.layernorm_grad_ws_numel(x.numel() // c, c),), torch.float32) if need_dp else None
+            be.layernorm_grad(x, dy, gamma, dx=dx, dgamma=dg, dbeta=db, ws=ws, eps=ctx.eps)
         return dx, dg if need_g else None, db if need_b else None, None, None
 
 
-class _Geglu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, be):
-        _check16(h, "h")
-        if h.shape[-1] % 16:
-            raise ValueError(f"geglu takes h [..., 2F] with F a multiple of 8, got {tuple(h.shape)}")
-        h = h.contiguous()
-        be.wait_current()
-        y = be.empty(h.shape[:-1] + (h.shape[-1] // 2,), h.dtype)
-        be.geglu(h, y)
-        be.release_to_current()
-        ctx.save_for_backward(h)
-        ctx.be = be
-        return y
+class _Pointwise(torch.autograd.Function):
+    """``op`` = "gelu": x [..., F] -> [..., F]; "geglu": h [..., 2F] -> [..., F].  Forward ``be.<op>(x, y)``, backward
+    ``be.<op>_grad(x, dy, dx)`` on the saved input."""
 
     @staticmethod
-    def backward(ctx, dy):
-        (h,) = ctx.saved_tensors
-        be = ctx.be
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        dy = dy.to(h.dtype).contiguous()
-        be.wait_current()
-        dh = be.empty(tuple(h.shape), h.dtype)
-        be.geglu_grad(h, dy, dh)
-        be.release_to_current()
-        return dh, None
-
-
-class _Gelu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, be):
-        _check16(x, "x")
-        if x.shape[-1] % 8:
-            raise ValueError(f"gelu takes x [..., F] with F a multiple of 8, got {tuple(x.shape)}")
+    def forward(ctx, x, be, op):
+        ratio, what = (2, "h [..., 2F]") if op == "geglu" else (1, "x [..., F]")
+        _check16(x, what[0])
+        if x.shape[-1] % (8 * ratio):
+            raise ValueError(f"{op} takes {what} with F a multiple of 8, got {tuple(x.shape)}")
         x = x.contiguous()
-        be.wait_current()
-        y = be.empty(tuple(x.shape), x.dtype)
-        be.gelu(x, y)
-        be.release_to_current()
+        with on_backend(be):
+            y = be.empty(x.shape[:-1] + (x.shape[-1] // ratio,), x.dtype)
+            getattr(be, op)(x, y)
         ctx.save_for_backward(x)
-        ctx.be = be
+        ctx.be, ctx.op = be, op
         return y
 
     @staticmethod
@@ -702,13 +680,12 @@ class _Gelu(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         be = ctx.be
         if not ctx.needs_input_grad[0]:
-            return None, None
+            return None, None, None
         dy = dy.to(x.dtype).contiguous()
-        be.wait_current()
-        dx = be.empty(tuple(x.shape), x.dtype)
-        be.gelu_grad(x, dy, dx)
-        be.release_to_current()
-        return dx, None
+        with on_backend(be):
+            dx = be.empty(tuple(x.shape), x.dtype)
+            getattr(be, ctx.op + "_grad")(x, dy, dx)
+        return dx, None, None
 
 
 class _PurifierGateTail(torch.autograd.Function):
@@ -721,10 +698,9 @@ class _PurifierGateTail(torch.autograd.Function):
                              f"{img.dtype}, {tuple(dis.shape)} {dis.dtype}, {tuple(z.shape)} {z.dtype}")
         _check_affine(gamma, beta, img.shape[-1])
         img, dis, z, gamma, beta = (t.contiguous() for t in (img, dis, z, gamma, beta))
-        be.wait_current()
-        out = be.empty(tuple(img.shape), torch.float32)
-        be.purifier_gate_tail(img, dis, z, gamma, beta, out, eps)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty(tuple(img.shape), torch.float32)
+            be.purifier_gate_tail(img, dis, z, gamma, beta, out, eps)
         ctx.save_for_backward(img, dis, z, gamma)
         ctx.be, ctx.eps = be, eps
         return out
@@ -739,14 +715,13 @@ class _PurifierGateTail(torch.autograd.Function):
             return (None,) * 7
         dout = dout.float().contiguous()
         c = img.shape[-1]
-        be.wait_current()
-        dimg, ddis, dz = (be.empty(tuple(img.shape), img.dtype) if need else None for need in (need_i, need_d, need_z))
-        dg = be.empty((c,), torch.float32) if need_dp else None
-        db = be.empty((c,), torch.float32) if need_dp else None
-        ws = be.empty((be.purifier_gate_tail_grad_ws_numel(img.numel() // c, c),), torch.float32) if need_dp else None
-        be.purifier_gate_tail_grad(img, dis, z, dout, gamma, dimg=dimg, ddis=ddis, dz=dz, dgamma=dg, dbeta=db, ws=ws,
-                                   eps=ctx.eps)
-        be.release_to_current()
+        with on_backend(be):
+            dimg, ddis, dz = (be.empty(tuple(img.shape), img.dtype) if need else None for need in (need_i, need_d, need_z))
+            dg = be.empty((c,), torch.float32) if need_dp else None
+            db = be.empty((c,), torch.float32) if need_dp else None
+            ws = be.empty((be.purifier_gate_tail_grad_ws_numel(img.numel() // c, c),), torch.float32) if need_dp else None
+            be.purifier_gate_tail_grad(img, dis, z, dout, gamma, dimg=dimg, ddis=ddis, dz=dz, dgamma=dg, dbeta=db, ws=ws,
+                                       eps=ctx.eps)
         return dimg, ddis, dz, dg if need_g else None, db if need_b else None, None, None
 
 
@@ -762,10 +737,9 @@ class _SelfAttention(torch.autograd.Function):
             raise ValueError(f"self_attention takes qkv [B,N,3C] with C a multiple of heads = {heads}, got {tuple(qkv.shape)}")
         qkv = qkv.contiguous()
         b, n, c3 = qkv.shape
-        be.wait_current()
-        out = be.empty((b, n, c3 // 3), qkv.dtype)
-        be.self_attn(qkv, out, heads)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty((b, n, c3 // 3), qkv.dtype)
+            be.self_attn(qkv, out, heads)
         ctx.save_for_backward(qkv)
         ctx.be, ctx.heads = be, heads
         return out
@@ -778,12 +752,11 @@ class _SelfAttention(torch.autograd.Function):
             return None, None, None
         c = qkv.shape[-1] // 3
         dy = dy.to(qkv.dtype).contiguous()
-        be.wait_current()
-        dqkv = be.empty(tuple(qkv.shape), qkv.dtype)
-        q, k, v = (qkv[..., i * c:(i + 1) * c] for i in range(3))
-        be.attn_grad(q, k, v, dy, dq=dqkv[..., :c], dk=dqkv[..., c:2 * c], dv=dqkv[..., 2 * c:], ws=_attn_ws(be, q, heads),
-                     heads=heads)
-        be.release_to_current()
+        with on_backend(be):
+            dqkv = be.empty(tuple(qkv.shape), qkv.dtype)
+            q, k, v = (qkv[..., i * c:(i + 1) * c] for i in range(3))
+            be.attn_grad(q, k, v, dy, dq=dqkv[..., :c], dk=dqkv[..., c:2 * c], dv=dqkv[..., 2 * c:], ws=_attn_ws(be, q, heads),
+                         heads=heads)
         return dqkv, None, None
 
 
@@ -797,10 +770,9 @@ class _Attention(torch.autograd.Function):
             raise ValueError(f"attention takes q [B,Nq,C] and k, v [B,Nk,C] of one 16-bit type, got {tuple(q.shape)} "
                              f"{tuple(k.shape)} {tuple(v.shape)}")
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        be.wait_current()
-        out = be.empty(tuple(q.shape), q.dtype)
-        be.attention(q, k, v, out, heads)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty(tuple(q.shape), q.dtype)
+            be.attention(q, k, v, out, heads)
         ctx.save_for_backward(q, k, v)
         ctx.be, ctx.heads = be, heads
         return out
@@ -813,12 +785,11 @@ class _Attention(torch.autograd.Function):
         if not (need_q or need_k or need_v):
             return (None,) * 5
         dy = dy.to(q.dtype).contiguous()
-        be.wait_current()
-        dq = be.empty(tuple(q.shape), q.dtype) if need_q else None
-        dk = be.empty(tuple(k.shape), q.dtype) if need_k else None
-        dv = be.empty(tuple(v.shape), q.dtype) if need_v else None
-        be.attn_grad(q, k, v, dy, dq=dq, dk=dk, dv=dv, ws=_attn_ws(be, q, heads), heads=heads)
-        be.release_to_current()
+        with on_backend(be):
+            dq = be.empty(tuple(q.shape), q.dtype) if need_q else None
+            dk = be.empty(tuple(k.shape), q.dtype) if need_k else None
+            dv = be.empty(tuple(v.shape), q.dtype) if need_v else None
+            be.attn_grad(q, k, v, dy, dq=dq, dk=dk, dv=dv, ws=_attn_ws(be, q, heads), heads=heads)
         return dq, dk, dv, None, None
 
 
@@ -836,10 +807,9 @@ class _TriCrossAttention(torch.autograd.Function):
             raise ValueError("tri_cross_attention: split mode takes gates, a device fp32[2] buffer")
         q, kv = q.contiguous(), kv.contiguous()
         gates = None if gates is None else gates.contiguous()
-        be.wait_current()
-        out = be.empty(tuple(q.shape), q.dtype)
-        be.tri_xattn(q, kv, out, gates, lam, mode, heads)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty(tuple(q.shape), q.dtype)
+            be.tri_xattn(q, kv, out, gates, lam, mode, heads)
         ctx.save_for_backward(q, kv, gates)
         ctx.be, ctx.cfg = be, (lam, heads, mode)
         return out
@@ -860,27 +830,26 @@ class _TriCrossAttention(torch.autograd.Function):
                 paths.append((32, 16, 2 * c, float(lam), None))                          # delta, skipped as in the forward
         else:
             paths = [(0, 32, 0, 1.0, None)]
-        be.wait_current()
-        dkv = be.zeros(tuple(kv.shape), kv.dtype) if need_kv else None
-        ws = _attn_ws(be, q, heads)
-        dqs = []
-        for t0, nt, kc, scale, scale_dev in paths:
-            k, v = kv[:, t0:t0 + nt, kc:kc + c], kv[:, t0:t0 + nt, kc + c:kc + 2 * c]
-            dq = be.empty(tuple(q.shape), q.dtype) if need_q else None
-            dk = dkv[:, t0:t0 + nt, kc:kc + c] if need_kv else None
-            dv = dkv[:, t0:t0 + nt, kc + c:kc + 2 * c] if need_kv else None
-            be.attn_grad(q, k, v, dy, dq=dq, dk=dk, dv=dv, ws=ws, heads=heads, do_scale=scale, do_scale_dev=scale_dev)
-            dqs.append(dq)
-        dq = None
-        if need_q:
-            dq = dqs[0]
-            if len(dqs) > 1:
-                with be.ctx():      # fp32 sum of the pathways' dq, rounded once
-                    acc = dqs[0].float()
-                    for t in dqs[1:]:
-                        acc += t.float()
-                    dq = acc.to(q.dtype)
-        be.release_to_current()
+        with on_backend(be):
+            dkv = be.zeros(tuple(kv.shape), kv.dtype) if need_kv else None
+            ws = _attn_ws(be, q, heads)
+            dqs = []
+            for t0, nt, kc, scale, scale_dev in paths:
+                k, v = kv[:, t0:t0 + nt, kc:kc + c], kv[:, t0:t0 + nt, kc + c:kc + 2 * c]
+                dq = be.empty(tuple(q.shape), q.dtype) if need_q else None
+                dk = dkv[:, t0:t0 + nt, kc:kc + c] if need_kv else None
+                dv = dkv[:, t0:t0 + nt, kc + c:kc + 2 * c] if need_kv else None
+                be.attn_grad(q, k, v, dy, dq=dq, dk=dk, dv=dv, ws=ws, heads=heads, do_scale=scale, do_scale_dev=scale_dev)
+                dqs.append(dq)
+            dq = None
+            if need_q:
+                dq = dqs[0]
+                if len(dqs) > 1:
+                    with be.ctx():      # fp32 sum of the pathways' dq, rounded once
+                        acc = dqs[0].float()
+                        for t in dqs[1:]:
+                            acc += t.float()
+                        dq = acc.to(q.dtype)
         return dq, dkv, None, None, None, None, None
 
 
@@ -924,13 +893,13 @@ def layer_norm(be, x, gamma, beta, eps=1e-5):
 
 def geglu(be, h):
     """h [..., 2F] -> h[..., :F] * gelu(h[..., F:]) (the chunk(2) order of the reference model); differentiable in h."""
-    return _Geglu.apply(h, be)
+    return _Pointwise.apply(h, be, "geglu")
 
 
 def gelu(be, x):
     """Exact-form GELU of x [..., F] (F a multiple of 8), the activation of the conditioning front-end's MLPs;
     differentiable in x (``HipBackend.gelu`` / ``gelu_grad``, csrc/cond_grad.hip)."""
-    return _Gelu.apply(x, be)
+    return _Pointwise.apply(x, be, "gelu")
 
 
 def purifier_gate_tail(be, img, dis, z, gamma, beta, eps=1e-5):

@@ -12,29 +12,31 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdadd_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("igemm.hip", "igemm_dma.hip", "conv_halo.hip", "attn2_fused.hip", "ffn_block.hip", "tf_head.hip", "norm.hip", "attention.hip", "elementwise.hip",
-           "conditioning.hip", "api.hip",
-           # bf16 twins of the UNet's generic-path kernels (csrc/bf16_names.h)
-           "igemm_bf16.hip", "igemm_dma_bf16.hip", "conv_halo_bf16.hip", "norm_bf16.hip", "attention_bf16.hip",
-           "elementwise_bf16.hip",
-           # training backward: the M-reduction GEMM of the weight gradient and its bf16 twin
-           "wgrad.hip", "wgrad_bf16.hip",
-           # training backward: GroupNorm(+SiLU) / LayerNorm / GEGLU and the plain GEGLU forward, and their bf16 twin
-           "norm_grad.hip", "norm_grad_bf16.hip",
-           # training backward: attention (statistics, dK / dV, dQ) and its bf16 twin
-           "attn_grad.hip", "attn_grad_bf16.hip",
-           # training backward: the data gradient of the stride-2 and upsampled 3x3 convs and its bf16 twin
-           "dgrad.hip", "dgrad_bf16.hip",
-           # training backward: weight / bias gradient of the 4-channel end convs and the loss gradient, and its bf16 twin
-           "end_grad.hip", "end_grad_bf16.hip",
-           # training, conditioning front-end: GELU and its derivative, the purifier's gated tail and its backward, bf16 twin
-           "cond_grad.hip", "cond_grad_bf16.hip",
-           # training backward of the fp32 row path: linear_rows, aoe_interp and the EPI_ROWVEC row (the last one has the bf16 twin)
-           "rows_grad.hip", "rows_grad_bf16.hip",
-           # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (one source, no bf16 twin)
-           "optim.hip",
-           # training: one-launch re-layout of the 16-bit weights for the data gradients, and its bf16 twin
-           "relayout.hip", "relayout_bf16.hip")
+# sources compiled once (fp16 only, or no 16-bit kernel of their own)
+_SINGLE_SOURCES = ("attn2_fused", "ffn_block", "tf_head", "conditioning", "api",
+                   # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (the 16-bit type is a flag)
+                   "optim")
+# sources compiled a second time as NAME_bf16.hip, the bf16 twin (csrc/bf16_names.h)
+_TWINNED_SOURCES = (
+    # the UNet's generic-path kernels
+    "igemm", "igemm_dma", "conv_halo", "norm", "attention", "elementwise",
+    # training backward: the M-reduction GEMM of the weight gradient
+    "wgrad",
+    # training backward: GroupNorm(+SiLU) / LayerNorm / GEGLU and the plain GEGLU forward
+    "norm_grad",
+    # training backward: attention (statistics, dK / dV, dQ)
+    "attn_grad",
+    # training backward: the data gradient of the stride-2 and upsampled 3x3 convs
+    "dgrad",
+    # training backward: weight / bias gradient of the 4-channel end convs and the loss gradient
+    "end_grad",
+    # training, conditioning front-end: GELU and its derivative, the purifier's gated tail and its backward
+    "cond_grad",
+    # training backward of the fp32 row path: linear_rows, aoe_interp and the EPI_ROWVEC row (only the last one is in the twin)
+    "rows_grad",
+    # training: one-launch re-layout of the 16-bit weights for the data gradients
+    "relayout")
+SOURCES = tuple(s + ".hip" for s in _SINGLE_SOURCES) + tuple(s + sfx for s in _TWINNED_SOURCES for sfx in (".hip", "_bf16.hip"))
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_GEGLU = 1, 2, 4, 8
@@ -112,8 +114,19 @@ class AttnGradDesc(C.Structure):
                [("do_scale", f32)]
 
 
+def _with_bf16(table, stems=None):
+    """``table`` with a ``_bf16`` entry behind each ``_f16`` entry of ``stems`` (default: behind every one), carrying the
+    prototype of its original: a twin takes the same argument list."""
+    out = {}
+    for name, proto in table.items():
+        out[name] = proto
+        if name.endswith("_f16") and (stems is None or name[:-len("_f16")] in stems):
+            out[name[:-len("_f16")] + "_bf16"] = proto
+    return out
+
+
 # name -> (restype, argtypes); every symbol include/dadd_hip.h declares
-PROTOTYPES = {
+PROTOTYPES = _with_bf16({
     "dadd_last_error": (C.c_char_p, []),
     "dadd_version": (C.c_int, []),
     "dadd_init": (C.c_int, []),
@@ -150,20 +163,6 @@ PROTOTYPES = {
     "dadd_clip_patch_rows_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "dadd_aoe_interp_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "dadd_purifier_tail_f16": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
-    # bf16 siblings: same argument lists as the _f16 entry points
-    "dadd_conv_igemm_bf16": (C.c_int, [C.POINTER(IgemmDesc), vp]),
-    "dadd_conv_in_nchw_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
-    "dadd_conv3x3_cout4_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, vp]),
-    "dadd_conv_out_ddim_bf16": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-    "dadd_groupnorm_bf16": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
-                                      C.c_int, f32, C.c_int, C.c_int, vp]),
-    "dadd_layernorm_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
-    "dadd_self_attn_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, vp]),
-    "dadd_attn_bf16": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 8 + [vp]),
-    "dadd_tri_xattn_bf16": (C.c_int, [vp, vp, vp, vp, f32, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, vp]),
     "dadd_conv_wgrad_f16": (C.c_int, [C.POINTER(WgradDesc), vp]),
     "dadd_begin_step": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "dadd_ddim_update_f32": (C.c_int, [vp, vp, vp, f32, vp, vp, i64, vp]),
@@ -176,80 +175,61 @@ PROTOTYPES = {
     "dadd_prof_begin": (C.c_int, []),
     "dadd_prof_end": (C.c_int, [C.POINTER(C.c_int)]),
     "dadd_prof_record": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double)]),
-}
+}, stems=("dadd_conv_igemm", "dadd_conv_in_nchw", "dadd_conv3x3_cout4", "dadd_conv_out_ddim", "dadd_groupnorm", "dadd_layernorm",
+          "dadd_self_attn", "dadd_attn", "dadd_tri_xattn"))       # the bf16 siblings this header declares
 
 # every symbol include/dadd_hip_host.h declares (host-only: what a descriptor would launch, csrc/igemm.hip resolve)
-HOST_PROTOTYPES = {
-    "dadd_conv_igemm_resolve_bf16": (C.c_int, [C.POINTER(IgemmDesc), C.c_int, C.POINTER(IgemmChoice)]),
-}
+HOST_PROTOTYPES = {"dadd_conv_igemm_resolve_bf16": PROTOTYPES["dadd_conv_igemm_resolve_f16"]}
 
 # every symbol include/dadd_hip_grad.h declares (training backward only)
-GRAD_PROTOTYPES = {
-    "dadd_conv_wgrad_bf16": (C.c_int, [C.POINTER(WgradDesc), vp]),
-}
+GRAD_PROTOTYPES = {"dadd_conv_wgrad_bf16": PROTOTYPES["dadd_conv_wgrad_f16"]}
 
 # every symbol include/dadd_hip_norm_grad.h declares (training backward of the norms and GEGLU, csrc/norm_grad.hip)
-_LN_GRAD = (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp])
-NORM_GRAD_PROTOTYPES = {
+NORM_GRAD_PROTOTYPES = _with_bf16({
     "dadd_groupnorm_grad_f16": (C.c_int, [C.POINTER(GnGradDesc), vp]),
-    "dadd_groupnorm_grad_bf16": (C.c_int, [C.POINTER(GnGradDesc), vp]),
     "dadd_groupnorm_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "dadd_layernorm_grad_f16": _LN_GRAD,
-    "dadd_layernorm_grad_bf16": _LN_GRAD,
+    "dadd_layernorm_grad_f16": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
     "dadd_layernorm_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int]),
     "dadd_geglu_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
-    "dadd_geglu_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "dadd_geglu_grad_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-    "dadd_geglu_grad_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-}
+})
 
 # every symbol include/dadd_hip_attn_grad.h declares (training backward of attention, csrc/attn_grad.hip)
-ATTN_GRAD_PROTOTYPES = {
+ATTN_GRAD_PROTOTYPES = _with_bf16({
     "dadd_attn_grad_f16": (C.c_int, [C.POINTER(AttnGradDesc), vp]),
-    "dadd_attn_grad_bf16": (C.c_int, [C.POINTER(AttnGradDesc), vp]),
     "dadd_attn_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
-}
+})
 
 # every symbol include/dadd_hip_dgrad.h declares (data gradient of the stride-2 / upsampled 3x3 conv, csrc/dgrad.hip)
-DGRAD_PROTOTYPES = {
+DGRAD_PROTOTYPES = _with_bf16({
     "dadd_conv_dgrad_f16": (C.c_int, [C.POINTER(DgradDesc), vp]),
-    "dadd_conv_dgrad_bf16": (C.c_int, [C.POINTER(DgradDesc), vp]),
     "dadd_conv_dgrad_resolve": (C.c_int, [C.POINTER(DgradDesc), C.POINTER(DgradChoice)]),
-}
+})
 
 # every symbol include/dadd_hip_end_grad.h declares (gradients of the 4-channel end convs and of the loss, csrc/end_grad.hip)
-END_GRAD_PROTOTYPES = {
+END_GRAD_PROTOTYPES = _with_bf16({
     "dadd_conv_end_wgrad_f16": (C.c_int, [C.POINTER(EndWgradDesc), vp]),
-    "dadd_conv_end_wgrad_bf16": (C.c_int, [C.POINTER(EndWgradDesc), vp]),
     "dadd_end_wgrad_partial_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "dadd_mse_rows_grad_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, i64, vp]),
-}
+})
 
 # every symbol include/dadd_hip_cond_grad.h declares (training kernels of the conditioning front-end, csrc/cond_grad.hip)
-_GATE_TAIL = (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp])
-_GATE_TAIL_GRAD = (C.c_int, [vp] * 11 + [C.c_int, C.c_int, f32, vp])
-COND_GRAD_PROTOTYPES = {
+COND_GRAD_PROTOTYPES = _with_bf16({
     "dadd_gelu_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
-    "dadd_gelu_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "dadd_gelu_grad_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-    "dadd_gelu_grad_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-    "dadd_purifier_gate_tail_f16": _GATE_TAIL,
-    "dadd_purifier_gate_tail_bf16": _GATE_TAIL,
-    "dadd_purifier_gate_tail_grad_f16": _GATE_TAIL_GRAD,
-    "dadd_purifier_gate_tail_grad_bf16": _GATE_TAIL_GRAD,
+    "dadd_purifier_gate_tail_f16": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
+    "dadd_purifier_gate_tail_grad_f16": (C.c_int, [vp] * 11 + [C.c_int, C.c_int, f32, vp]),
     "dadd_purifier_gate_tail_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int]),
-}
+})
 
 # every symbol include/dadd_hip_rows_grad.h declares (backward of the fp32 row path, csrc/rows_grad.hip)
-_ROWVEC_GRAD = (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp])
-ROWS_GRAD_PROTOTYPES = {
+ROWS_GRAD_PROTOTYPES = _with_bf16({
     "dadd_linear_rows_grad_f32": (C.c_int, [vp] * 7 + [C.c_int] * 5 + [vp]),
     "dadd_linear_rows_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "dadd_aoe_interp_grad_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-    "dadd_rowvec_grad_f16": _ROWVEC_GRAD,
-    "dadd_rowvec_grad_bf16": _ROWVEC_GRAD,
+    "dadd_rowvec_grad_f16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "dadd_rowvec_grad_ws_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
-}
+})
 
 # include/dadd_hip_optim.h: the optimizer step (csrc/optim.hip)
 OPTIM_CHUNK, OPTIM_MAX_GROUPS = 4096, 8
@@ -290,14 +270,32 @@ class RelayoutDesc(C.Structure):
 
 
 # every symbol include/dadd_hip_relayout.h declares
-_RELAYOUT = (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, vp])
-RELAYOUT_PROTOTYPES = {
+RELAYOUT_PROTOTYPES = _with_bf16({
     "dadd_relayout_tiles": (C.c_longlong, [C.c_int] * 4),
     "dadd_relayout_dst_numel": (C.c_longlong, [C.c_int] * 4),
     "dadd_dgrad_relayout_plan": (C.c_longlong, [C.POINTER(RelayoutDesc), C.c_int, C.c_longlong, C.c_longlong]),
-    "dadd_dgrad_relayout_f16": _RELAYOUT,
-    "dadd_dgrad_relayout_bf16": _RELAYOUT,
+    "dadd_dgrad_relayout_f16": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, vp]),
+})
+
+# The registry: header under include/ -> the table of what it declares.  A new header is one entry here; load(), the
+# dependencies of build() and the symbol check of __graft_entry__.build() follow.
+HEADER_PROTOTYPES = {
+    "dadd_hip.h": PROTOTYPES,
+    "dadd_hip_host.h": HOST_PROTOTYPES,
+    "dadd_hip_grad.h": GRAD_PROTOTYPES,
+    "dadd_hip_norm_grad.h": NORM_GRAD_PROTOTYPES,
+    "dadd_hip_attn_grad.h": ATTN_GRAD_PROTOTYPES,
+    "dadd_hip_dgrad.h": DGRAD_PROTOTYPES,
+    "dadd_hip_end_grad.h": END_GRAD_PROTOTYPES,
+    "dadd_hip_cond_grad.h": COND_GRAD_PROTOTYPES,
+    "dadd_hip_rows_grad.h": ROWS_GRAD_PROTOTYPES,
+    "dadd_hip_optim.h": OPTIM_PROTOTYPES,
+    "dadd_hip_relayout.h": RELAYOUT_PROTOTYPES,
 }
+ALL_PROTOTYPES = {}
+for _header, _table in HEADER_PROTOTYPES.items():
+    assert not ALL_PROTOTYPES.keys() & _table.keys(), (_header, sorted(ALL_PROTOTYPES.keys() & _table.keys()))
+    ALL_PROTOTYPES.update(_table)
 
 _lib: Optional[C.CDLL] = None
 
@@ -307,10 +305,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     import glob
     deps = sorted(set(srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))) + \
-        [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("dadd_hip.h", "dadd_hip_grad.h", "dadd_hip_host.h", "dadd_hip_norm_grad.h",
-                                                                       "dadd_hip_attn_grad.h", "dadd_hip_optim.h", "dadd_hip_dgrad.h",
-                                                                       "dadd_hip_end_grad.h", "dadd_hip_cond_grad.h", "dadd_hip_rows_grad.h",
-                                                                       "dadd_hip_relayout.h")]
+        [os.path.join(os.path.dirname(_HERE), "include", h) for h in HEADER_PROTOTYPES]
     if (not force and os.path.exists(LIB_PATH)
             and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
         return LIB_PATH
@@ -336,9 +331,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP extension is required (run __graft_entry__.build()); "
             "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**PROTOTYPES, **HOST_PROTOTYPES, **GRAD_PROTOTYPES, **NORM_GRAD_PROTOTYPES,
-                              **ATTN_GRAD_PROTOTYPES, **OPTIM_PROTOTYPES, **DGRAD_PROTOTYPES, **END_GRAD_PROTOTYPES,
-                              **COND_GRAD_PROTOTYPES, **ROWS_GRAD_PROTOTYPES, **RELAYOUT_PROTOTYPES}.items():
+    for name, (res, args) in ALL_PROTOTYPES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -15,8 +15,8 @@ from progressive_stable_diffusion_amd import weights as W
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_functions():
-    text = open(os.path.join(ROOT, "include", "dadd_hip.h")).read()
+def _header_functions(header="dadd_hip.h"):
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(dadd_[a-z0-9_]+)\s*\(", text)))
 
@@ -31,6 +31,29 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, n), f"{n} declared in dadd_hip.h but not exported"
     assert set(names) == set(L.PROTOTYPES), set(names) ^ set(L.PROTOTYPES)
     assert handle.dadd_version() == 100
+
+
+def test_registry_covers_every_header_exactly():
+    """``lib.HEADER_PROTOTYPES`` has one table per header under include/, with exactly the functions that header
+    declares; the tables are pairwise disjoint, their union is ``lib.ALL_PROTOTYPES``, and the library exports all of it."""
+    headers = sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
+    assert headers == sorted(L.HEADER_PROTOTYPES)
+    for h in headers:
+        declared = set(_header_functions(h))
+        assert declared == set(L.HEADER_PROTOTYPES[h]), (h, declared ^ set(L.HEADER_PROTOTYPES[h]))
+    tables = list(L.HEADER_PROTOTYPES.values())
+    for i, a in enumerate(tables):
+        for b in tables[i + 1:]:
+            assert not set(a) & set(b), set(a) & set(b)
+    union = {}
+    for t in tables:
+        union.update(t)
+    assert union == L.ALL_PROTOTYPES and len(L.ALL_PROTOTYPES) == sum(len(t) for t in tables)
+    handle = ctypes.CDLL(L.build())
+    assert not [n for n in L.ALL_PROTOTYPES if not hasattr(handle, n)]
+    # ... and the names __graft_entry__.build() requires of the library are that union, no table forgotten
+    import __graft_entry__ as G
+    assert G.entry_points() == list(L.ALL_PROTOTYPES)
 
 
 def test_igemm_desc_layout_matches_header(tmp_path):
