@@ -10,17 +10,26 @@ fp32 masters, taken from the module's state dict once; the module's inference pl
 state_dict=...)`` loads.
 
 Operands are fp16: the conditioning front-end's attention (d = 96) has no bf16 forward, so bf16 is refused here.
+
+A run on top of the step: ``backward()`` / ``optimizer_step()`` / ``flush()`` accumulate micro-batches
+(``accumulate_grad_batches``), a small device block collects the run's numbers until ``pop_metrics()`` fetches them with
+one synchronisation, ``state()`` / ``load_state()`` / ``save_checkpoint()`` / ``resume()`` keep everything an exact
+continuation needs in the layout of ``training_io``, and ``fit()`` is the epoch loop over any re-iterable of batches.
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
 
 from . import conditioning_grad as CG
+from . import checkpoint as CK
 from . import grad_ops as G
+from . import lib as L
 from . import optim as O
+from . import training_io as IO
 from . import unet_grad as UG
 from .lr_scheduler import warmup_cosine_lr
 
@@ -40,10 +49,11 @@ class Trainer:
     ``cfg.training`` with the reference's defaults where the key is missing: ``gradient_clip_val`` 1.0, ``ema_decay``
     0.999, ``update_starting_at_step`` 100, ``update_every_n_steps`` 4, ``max_epochs`` 150, ``use_min_snr_weighting``;
     from ``cfg.optimizer`` ``betas`` / ``weight_decay`` and from ``cfg.scheduler`` ``warmup_epochs`` / ``min_lr``.
-    ``prepared=False`` runs every product on the masters alone (cast and torch re-layout per call)."""
+    ``prepared=False`` runs every product on the masters alone (cast and torch re-layout per call).  ``accumulate``:
+    micro-batches per optimizer step; ``None`` reads ``cfg.training.accumulate_grad_batches`` (default 1)."""
 
     def __init__(self, module, lr: float, *, prepared: bool = True, operand_dtype: torch.dtype = torch.float16,
-                 init_scale: Optional[float] = None, growth_interval: int = 2000):
+                 init_scale: Optional[float] = None, growth_interval: int = 2000, accumulate: Optional[int] = None):
         if operand_dtype != torch.float16:
             raise ValueError(f"Trainer runs in fp16: the conditioning front-end's attention (d = 96) has no {operand_dtype} "
                              "forward, so a training step in that type is not available")
@@ -58,6 +68,10 @@ class Trainer:
         self.ema_decay = float(_get(tr, "ema_decay", 0.999))
         self.ema_start = int(_get(tr, "update_starting_at_step", 100))
         self.ema_every = max(1, int(_get(tr, "update_every_n_steps", 4)))
+        self.accumulate = int(_get(tr, "accumulate_grad_batches", 1) if accumulate is None else accumulate)
+        if self.accumulate < 1:
+            raise ValueError(f"accumulate_grad_batches must be at least 1, got {self.accumulate}")
+        self.log_every = max(1, int(_get(tr, "log_every_n_steps", 50)))
         if init_scale is None:
             init_scale = 65536.0 if str(_get(tr, "precision", "16-mixed")) == "16-mixed" else 0.0
         self.loss_scaling = float(init_scale) > 0.0      # (a scale of 0 in the state block means: no loss scaling)
@@ -87,6 +101,18 @@ class Trainer:
             self.relayout.refresh()
         self.steps = 0
         self.epoch = 0
+        self.pending = 0                    # micro-batches in the arena's g that no optimizer step has taken yet
+        self.ema_latest_step = 0            # the optimizer step of the last EMA update (the callback's latest_update_step)
+        self.next_epoch = 0                 # where fit() starts: 0, or the epoch after a loaded state's
+        # the run's numbers, on the device: sum of micro losses, sum of CFG drop rates, micro-batches, skipped steps
+        self._metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._sums = [self._metrics[i] for i in range(3)]       # views, made once: one fused add per micro-batch
+        self._skipped = self._metrics[3:4]
+        self._one = torch.ones((), dtype=torch.float32, device=self.device)
+        self._found_inf = self.optimizer.state[L.OptimState.found_inf.offset // 4:L.OptimState.found_inf.offset // 4 + 1]
+        self._last_drop = None
+        self._writer = IO.BackgroundWriter()
+        self._copy_stream = None
         self._lrs = None
         self.set_epoch(0)
 
@@ -143,6 +169,7 @@ class Trainer:
         img = img.float()
         if drop_mask is None:
             drop_mask = torch.rand(b, device=self.device) < getattr(mod.cfg.model, "cfg_drop_prob", 0.1)
+        self._last_drop = drop_mask
         img = torch.where(drop_mask.to(self.device).view(-1, 1, 1).expand_as(img), torch.zeros_like(img), img)
         cond = torch.cat([aoe, img, torch.zeros_like(aoe)] if dc.use_routing_gates else [aoe, img], dim=1)
         pred = UG.unet_forward(be, P, noisy, t, cond, use_routing_gates=dc.use_routing_gates,
@@ -154,17 +181,81 @@ class Trainer:
     def step(self, batch, **draws) -> torch.Tensor:
         """loss x loss scale -> backward (into the arena's gradient buffer) -> ``FusedAdamW.step`` (with the EMA on the
         reference's cadence) -> re-layout refresh -> learning rates.  No host synchronisation; returns the unscaled loss
-        (detached, on the device)."""
+        (detached, on the device).
+        With ``accumulate`` = k > 1 every call runs the backward with its loss weighted 1 / k and every k-th call the
+        optimizer step; ``flush()`` steps for a short last group."""
+        loss = self.backward(batch, weight=1.0 / self.accumulate, **draws)
+        if IO.optimizer_step_due(self.pending, self.accumulate):
+            self.optimizer_step()
+        return loss
+
+    def backward(self, batch, *, weight: float = 1.0, **draws) -> torch.Tensor:
+        """One micro-batch: ``loss()``, then ``(loss * weight * loss scale).backward()``, which ADDS into the arena's
+        gradient buffer (``ParamArena.attach``).  No optimizer call; the micro-batch counts as pending until
+        ``optimizer_step()``.  Returns the unscaled, unweighted loss (detached, on the device) and adds it to the run's
+        numbers.  No host synchronisation."""
         loss = self.loss(batch, **draws)
-        scale = self.optimizer.scale()          # a device scalar: no sync
-        (loss * scale if self.loss_scaling else loss).backward()
+        factor = self.optimizer.scale() if self.loss_scaling else None      # a device scalar: no sync
+        if weight != 1.0:
+            factor = weight if factor is None else factor * weight
+        (loss if factor is None else loss * factor).backward()
+        self.pending += 1
+        out = loss.detach()
+        drop = self._last_drop.to(self.device).mean(dtype=torch.float32)
+        torch._foreach_add_(self._sums, [out, drop, self._one])
+        return out
+
+    def optimizer_step(self) -> None:
+        """The optimizer step on what the pending micro-batches left in the gradient buffer: ``FusedAdamW.step`` (clip,
+        unscale, AdamW, 16-bit copy, zeroed gradient; the EMA when ``training_io.ema_due`` says so - ``steps`` and the
+        cadence count optimizer steps, not micro-batches), re-layout refresh, learning rates.  No host synchronisation."""
+        if self.pending == 0:
+            raise RuntimeError("optimizer_step(): no micro-batch is pending (backward() first)")
         self.steps += 1
-        update_ema = self.steps >= self.ema_start and self.steps % self.ema_every == 0
+        update_ema = IO.ema_due(self.steps, self.ema_start, self.ema_every)
         self.optimizer.step(update_ema=update_ema, zero_grad=True)
+        if update_ema:
+            self.ema_latest_step = self.steps
         if self.relayout is not None:
             self.relayout.refresh()
+        self._skipped.add_(self._found_inf)             # 1 when the step was skipped for a non-finite gradient
         self.set_epoch(self.epoch)
-        return loss.detach()
+        self.pending = 0
+
+    def flush(self) -> bool:
+        """The optimizer step for a short last group (fewer than ``accumulate`` micro-batches pending, as at the end of
+        an epoch whose length is no multiple of k); nothing when none is pending.  The group keeps the weight 1 / k per
+        micro-batch: its gradient is the sum over its j < k losses divided by k, not by j, so a short group weighs j / k
+        of a full one - what Lightning's ``accumulate_grad_batches`` does with the last batches of an epoch, and the rule
+        under which a sample counts the same wherever it falls.  -> whether a step ran."""
+        if self.pending == 0:
+            return False
+        self.optimizer_step()
+        return True
+
+    # -- the run's numbers
+    METRIC_KEYS = ("loss", "cfg_drop_rate", "micro_batches", "skipped_steps", "step", "grad_norm", "coef", "found_inf",
+                   "scale", "growth_tracker", "lr", "epoch", "global_step")
+
+    def pop_metrics(self) -> dict:
+        """What the run has collected since the last call, and one synchronisation to fetch it: ``loss`` (mean of the
+        unscaled micro losses) and ``cfg_drop_rate`` (mean share of dropped samples) over ``micro_batches``,
+        ``skipped_steps`` (optimizer steps the loss scaler skipped), ``optimizer.stats()``' ``step, grad_norm, coef,
+        found_inf, scale, growth_tracker`` of the last step, ``lr`` (group name -> the rate in the state block now),
+        ``epoch`` and ``global_step`` (optimizer steps of the run).  The device block is zeroed; means of an empty block
+        are NaN."""
+        be, words = self.be, self.optimizer.state.numel()
+        be.wait_current()
+        with be.ctx():
+            blob = torch.cat([self.optimizer.state, self._metrics.view(torch.int32)]).cpu()     # the one sync
+        self._metrics.zero_()
+        h = L.OptimState.from_buffer_copy(blob[:words].numpy().tobytes())
+        loss_sum, drop_sum, n, skipped = blob[words:].view(torch.float32).tolist()
+        return {"loss": loss_sum / n if n else float("nan"), "cfg_drop_rate": drop_sum / n if n else float("nan"),
+                "micro_batches": int(n), "skipped_steps": int(skipped), "step": h.step, "grad_norm": h.grad_norm,
+                "coef": h.coef, "found_inf": bool(h.found_inf), "scale": h.scale, "growth_tracker": h.growth_tracker,
+                "lr": {g["name"]: float(h.lr[i]) for i, g in enumerate(self.groups)}, "epoch": self.epoch,
+                "global_step": self.steps}
 
     # -- export
     def export_state_dict(self, ema: bool = False) -> "OrderedDict[str, torch.Tensor]":
@@ -182,3 +273,154 @@ class Trainer:
             else:
                 masters[k] = view(k).detach().cpu()
         return UG.state_dict_from_masters(masters)
+
+    # -- state and checkpoints
+    def _untrained(self) -> List[str]:
+        return [k for k in self.module._sd if k.startswith(_FROZEN) or k in self.gates]
+
+    @staticmethod
+    def _to_masters(sd) -> Dict[str, torch.Tensor]:
+        out = dict(sd)
+        out.update(UG.masters_from_state_dict(sd))
+        return out
+
+    def state(self, device="cpu", parts: Sequence[str] = IO.PARTS) -> dict:
+        """Everything an exact continuation needs, as the dict of ``training_io`` with copies of every tensor on
+        ``device``: ``state_dict`` (the EMA; equal to ``export_state_dict(ema=True)``), ``current_model_state`` (the raw
+        weights; equal to ``export_state_dict()``), ``optimizer_states`` (moments, step, rates, loss scale and growth
+        tracker), the EMA bookkeeping, ``epoch`` / ``global_step`` and the states of torch's CPU generator and of this
+        device's.  ``parts`` leaves out what a reader does not need (``("ema",)`` is a weights-only file); only all three
+        restore a run.  The copies are taken on the backend's stream, behind every step issued so far; torch's stream
+        waits for them and for nothing else.  Raises ``RuntimeError`` while micro-batches are pending: their gradient is
+        not part of the state.  Synchronises (the optimizer's scalars go through the host)."""
+        if self.pending:
+            raise RuntimeError(f"{self.pending} micro-batch(es) are pending: flush() or optimizer_step() before the state is "
+                               "taken (the accumulated gradient is not part of it)")
+        device, be, sd = torch.device(device), self.be, self.module._sd
+        be.wait_current()
+        with be.ctx(), torch.no_grad():
+            shared = {k: (self.gates[k] if k in self.gates else sd[k]).detach().to(device=device, copy=True)
+                      for k in self._untrained()}
+
+            def export(view):
+                # the layout change on the arena's device is the copy; .to() moves it when ``device`` is another one
+                trained = UG.state_dict_from_masters(OrderedDict((k, view(k)) for k in self.arena.names))
+                for k, t in trained.items():
+                    if t._base is not None:     # a 1x1 conv's OIHW form is a view of the arena (already contiguous): copy it
+                        trained[k] = t.clone()
+                return OrderedDict((k, shared[k] if k in shared else trained[k].to(device)) for k in sd)
+            out = IO.pack(self.arena, self.optimizer, epoch=self.epoch, global_step=self.steps,
+                          latest_update_step=self.ema_latest_step, accumulate=self.accumulate, parts=parts, device=device,
+                          export=export, generators=IO.default_generators(self.device))
+        be.release_to_current()
+        if device.type == "cuda":           # allocated on the backend's stream, read by the caller on torch's
+            cur = torch.cuda.current_stream(self.device)
+            for part in (out["state_dict"], out.get("current_model_state", {})):
+                for t in part.values():
+                    t.record_stream(cur)
+            for st in (out["optimizer_states"][0]["state"].values() if "optimizer_states" in out else ()):
+                st["exp_avg"].record_stream(cur)
+                st["exp_avg_sq"].record_stream(cur)
+        return out
+
+    def load_state(self, state) -> None:
+        """Continue from a dict of ``state()`` (or a file of it read with ``checkpoint.read_raw``).  Names, shapes,
+        parameter groups, the operand type and the format tag are checked against this trainer first; a mismatch raises
+        ``ValueError`` naming the first offenders and changes nothing.  Restores the masters, the moments, the EMA, the
+        optimizer's step count, rates, loss scale and growth tracker, ``steps``, ``epoch``, the EMA bookkeeping and both
+        generators, then rebuilds the 16-bit working copy and the re-laid weights.  The step that follows computes what
+        the run that saved the state would have computed; ``fit()`` continues at the epoch after the state's (at the
+        state's own when it was taken before the first optimizer step)."""
+        if self.pending:
+            raise RuntimeError(f"{self.pending} micro-batch(es) are pending: flush() before a state is loaded")
+        self.be.release_to_current()        # the copies run on torch's stream, after what the backend still does
+        info = IO.load(state, self.arena, self.optimizer, to_masters=self._to_masters, ignore=self._untrained(),
+                       generators=IO.default_generators(self.device))
+        with torch.no_grad():
+            raw = state["current_model_state"]
+            for k, g in self.gates.items():
+                g.copy_(raw[k])
+            self.arena.g.zero_()
+            self._metrics.zero_()
+        self.steps, self.epoch = info["global_step"], info["epoch"]
+        self.next_epoch = self.epoch + (1 if self.steps > 0 else 0)      # a state from before the first step starts its epoch
+        self.ema_latest_step = info["latest_update_step"]
+        self._lrs = None                    # the rates are the file's until the next set_epoch()
+        if self.relayout is not None:
+            self.relayout.refresh()
+
+    def save_checkpoint(self, path, parts: Sequence[str] = IO.PARTS, wait: bool = True) -> str:
+        """``state()`` -> ``path``, written to ``path + ".tmp"`` and moved into place (``training_io.write_checkpoint``).
+        ``DiffusionModuleWithIP.load_from_checkpoint(path, which="ema" | "raw")`` and ``resume()`` read the file.
+
+        ``wait=False`` keeps the run going while the file is written: the state is snapshotted on the device (copies on
+        the backend's stream: the three parts are about 15 GB at full size, held until they have reached the host), and
+        one background thread brings the snapshot to the host and writes it.  Torch's stream waits for the snapshot
+        copies only.  A later save and ``close()`` wait for the write first; what the thread raised surfaces there."""
+        path = str(path)
+        self._writer.join()
+        if wait:
+            return IO.write_checkpoint(self.state("cpu", parts), path)
+        box = [self.state(self.device, parts)]
+        done = torch.cuda.Event()
+        done.record(self.be.stream)
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        device, stream = self.device, self._copy_stream
+
+        def job():
+            with torch.cuda.device(device):
+                done.synchronize()          # the writer waits for the snapshot, not the run
+                with torch.cuda.stream(stream):
+                    host = IO.to_host(box.pop())
+            IO.write_checkpoint(host, path)
+        self._writer.submit(job)
+        return path
+
+    def resume(self, path) -> None:
+        """``load_state`` of a file that ``save_checkpoint`` wrote with all three parts."""
+        self.load_state(CK.read_raw(str(path)))
+
+    def close(self) -> None:
+        """Wait for a background checkpoint write; re-raises what it raised."""
+        self._writer.join()
+
+    # -- the run
+    def fit(self, batches, *, epochs: Optional[int] = None, on_log: Optional[Callable[[dict], None]] = None,
+            log_every: Optional[int] = None, ckpt_dir=None, resume=None) -> List[dict]:
+        """Train over ``batches`` - any re-iterable of ``(images, labels, clip_pixel_values)``, iterated once per epoch -
+        up to epoch ``epochs`` (exclusive; default ``cfg.training.max_epochs``).  Per epoch: ``set_epoch``, ``step()``
+        per batch, ``flush()``, and with ``ckpt_dir`` a background ``save_checkpoint(ckpt_dir/last.ckpt)``.  After every
+        ``log_every``-th optimizer step (default ``cfg.training.log_every_n_steps``, 50) ``pop_metrics()`` is taken,
+        handed to ``on_log`` and kept; that is the loop's only synchronisation.  ``resume``: ``None``, ``"last"`` or a
+        path (``training_io.resolve_resume``); training continues at the epoch after the saved one (the position inside
+        an epoch is not kept: checkpoints are written at epoch ends).  A second call continues where the first stopped.
+        -> the logged dicts."""
+        path = IO.resolve_resume(resume, ckpt_dir)
+        if path is not None:
+            self.resume(path)
+        epochs = self.max_epochs if epochs is None else int(epochs)
+        log_every = self.log_every if log_every is None else max(1, int(log_every))
+        logged: List[dict] = []
+
+        def log():
+            if self.steps % log_every == 0:
+                logged.append(self.pop_metrics())
+                if on_log is not None:
+                    on_log(logged[-1])
+        try:
+            for e in range(self.next_epoch, epochs):
+                self.set_epoch(e)
+                for batch in batches:
+                    before = self.steps
+                    self.step(tuple(v.to(self.device, non_blocking=True) for v in batch))
+                    if self.steps != before:
+                        log()
+                if self.flush():
+                    log()
+                self.next_epoch = e + 1
+                if ckpt_dir is not None:
+                    self.save_checkpoint(os.path.join(str(ckpt_dir), IO.LAST), wait=False)
+        finally:
+            self.close()
+        return logged
