@@ -66,6 +66,13 @@ extern "C" {
 #define DADD_TUNE_SHALLOW 16 /* tuning: keep one K tile in flight instead of two (A/B measurements) */
 #define DADD_TUNE_NODMA 32   /* tuning: register-staged kernel instead of the LDS-DMA ring kernel */
 #define DADD_TUNE_PERSIST 64 /* tuning: LDS-DMA ring kept running over several output tiles per workgroup */
+#define DADD_TUNE_UPS_FOLD 131072 /* `ups` = 1 with `w_fold` given: run the upsampled 3x3 as four 2x2 phase convs on the un-upsampled
+                                     input with the pre-summed weights w_fold (K = 4 Cin instead of 9 Cin).  Taken by the 128-row
+                                     LDS-DMA kernel for one source, one K pass, pad 1, Ho = 2 Hi, Wo = 2 Wi, B*Hi*Wi a multiple of
+                                     128 (with DADD_EPI_GNSTAT: Hi*Wi a multiple of 64), bias / activation / GNSTAT epilogues; a
+                                     request outside that (no w_fold, split-K, 64-row tiles, DADD_TUNE_NODMA, ragged phases) runs
+                                     the 9-tap gather on `w` exactly as without the flag; residual, rowvec, x2 and LNSTAT with a
+                                     fold are refused */
 
 /* cross-attention modes of dadd_tri_xattn_f16 */
 #define DADD_XATTN_SPLIT 0    /* triple pathway, independent softmaxes */
@@ -129,6 +136,8 @@ typedef struct {
   const float* gn_out_gamma;
   const float* gn_out_beta;
   float gn_out_eps;
+  const void* w_fold;            /* DADD_TUNE_UPS_FOLD (see the flag): [4 phases = 2 py + px][N][4 taps (dy, dx)][Cin], each entry the
+                                    sum of the 1, 2 or 4 weights of `w` that land on that input pixel, rounded once; NULL: none */
 } dadd_igemm_desc;
 int dadd_conv_igemm_f16(const dadd_igemm_desc* d, void* stream);
 

@@ -40,7 +40,8 @@ def _sfx(*ts) -> str:
 
 def fill_igemm_desc(d, ptr, x, w, out, *, x2=None, bias=None, rowvec=None, residual=None, taps=1, stride=1,
                     ups=0, pad=0, flags=0, splitk=1, partial=None, tile_n=0, tile_m=0, counters=None, ln_c1=None,
-                    ln_eps=1e-5, gn_ws=None, gn_nchunk=0, ln_stats_out=None, ln_stats_in=None, gn_in=None, gn_apply=None):
+                    ln_eps=1e-5, gn_ws=None, gn_nchunk=0, ln_stats_out=None, ln_stats_in=None, gn_in=None, gn_apply=None,
+                    w_fold=None):
     """Check the shapes of one ``igemm`` call (arguments of ``HipBackend.igemm``) and fill the ``IgemmDesc`` ``d`` with
     it; ``ptr`` turns a tensor (or None) into the address the descriptor carries."""
     b, hi, wi, c1 = x.shape
@@ -94,6 +95,10 @@ def fill_igemm_desc(d, ptr, x, w, out, *, x2=None, bias=None, rowvec=None, resid
         d.gn_out, d.gn_out_gamma, d.gn_out_beta, d.gn_out_eps = ptr(g_out), ptr(gam), ptr(bet), float(eps_o)
     if partial is not None:
         assert partial.numel() >= splitk * b * ho * wo * n
+    d.w_fold = ptr(w_fold)
+    if w_fold is not None:      # the four phase weights of an upsample conv (engine.fold_ups_weight), beside the 9-tap ``w``
+        assert ups and taps == 9 and tuple(w_fold.shape) == (4, n, 4 * (c1 + c2)) and w_fold.dtype == w.dtype \
+            and w_fold.is_contiguous()
 
 
 class HipBackend:
@@ -111,6 +116,7 @@ class HipBackend:
         self._edesc = L.EndWgradDesc()
         self._gdesc = L.GnGradDesc()
         self._adesc = L.AttnGradDesc()
+        self._ups_folds = {}        # address of a 9-tap upsample-conv weight -> (that weight, its folded copy); register_ups_fold
         self._n_cu = None
         self._capturing = False     # between graph_begin() and graph_end(): no cross-stream waits may be recorded
         self._prof_on = False
@@ -266,6 +272,16 @@ class HipBackend:
         L.check(self.lib.dadd_gaussian_sample_f32(_p(mean), _p(logvar), _p(noise), float(scale), _p(out),
                                                   mean.numel(), self.s))
 
+    def register_ups_fold(self, w9, w4):
+        """``w4`` [4][N][4 Cin] is the phase-folded copy (``engine.fold_ups_weight``) of the packed upsample-conv weight
+        ``w9`` [N][9 Cin]: an ``igemm(..., w9, ups=1, flags=TUNE_UPS_FOLD)`` then runs the four 2x2 phase convs on it.
+        The registry holds both tensors, so neither address can be handed to another tensor while the entry exists; the
+        plan that registers owns them."""
+        if tuple(w4.shape) != (4, w9.shape[0], w9.shape[1] // 9 * 4) or w4.dtype != w9.dtype or not w4.is_contiguous() \
+                or w4.device != w9.device:
+            raise ValueError(f"register_ups_fold: w4 must be [4][N][4 Cin] of w9's type, got {tuple(w4.shape)} for {tuple(w9.shape)}")
+        self._ups_folds[w9.data_ptr()] = (w9, w4)
+
     def igemm(self, x, w, out, *, x2=None, bias=None, rowvec=None, residual=None, taps=1, stride=1,
               ups=0, pad=0, flags=0, splitk=1, partial=None, tile_n=0, tile_m=0, counters=None, ln_c1=None,
               ln_eps=1e-5, gn_ws=None, gn_nchunk=0, ln_stats_out=None, ln_stats_in=None, gn_in=None, gn_apply=None):
@@ -277,10 +293,12 @@ class HipBackend:
         ``ln_stats_in`` [P'][M][2] (EPI_LNFOLD): the partials of x written by its producer."""
         fn = getattr(self.lib, "dadd_conv_igemm_" + _sfx(x, x2, w, out, residual, None if gn_apply is None else gn_apply[0]))
         d = self._desc
+        fold = self._ups_folds.get(w.data_ptr()) if (flags & L.TUNE_UPS_FOLD) and ups else None
         fill_igemm_desc(d, _p, x, w, out, x2=x2, bias=bias, rowvec=rowvec, residual=residual, taps=taps, stride=stride,
                         ups=ups, pad=pad, flags=flags, splitk=splitk, partial=partial, tile_n=tile_n, tile_m=tile_m,
                         counters=counters, ln_c1=ln_c1, ln_eps=ln_eps, gn_ws=gn_ws, gn_nchunk=gn_nchunk,
-                        ln_stats_out=ln_stats_out, ln_stats_in=ln_stats_in, gn_in=gn_in, gn_apply=gn_apply)
+                        ln_stats_out=ln_stats_out, ln_stats_in=ln_stats_in, gn_in=gn_in, gn_apply=gn_apply,
+                        w_fold=None if fold is None else fold[1])
         L.check(fn(C.byref(d), self.s))
 
     # -- training backward of the matrix products (csrc/wgrad.hip; the data gradient is the forward kernel)

@@ -13,6 +13,7 @@
 #define splitk_finish_gn_kernel splitk_finish_gn_kernel_bf16
 #define splitk_finish_gnapply_kernel splitk_finish_gnapply_kernel_bf16
 #define igemm_dma_kernel igemm_dma_kernel_bf16
+#define igemm_ups_fold_kernel igemm_ups_fold_kernel_bf16
 #define conv3x3_halo_kernel conv3x3_halo_kernel_bf16
 #define gn_stats_kernel gn_stats_kernel_bf16
 #define gn_apply_kernel gn_apply_kernel_bf16
@@ -51,6 +52,8 @@
 #define dadd_init_igemm dadd_init_igemm_bf16
 #define dadd_init_igemm_dma dadd_init_igemm_dma_bf16
 #define dadd_igemm_dma_row dadd_igemm_dma_row_bf16
+#define dadd_init_igemm_ups_fold dadd_init_igemm_ups_fold_bf16
+#define dadd_igemm_ups_fold_row dadd_igemm_ups_fold_row_bf16
 #define dadd_igemm_resolve dadd_igemm_resolve_bf16
 #define dadd_init_conv_halo dadd_init_conv_halo_bf16
 #define dadd_conv_halo_applicable dadd_conv_halo_applicable_bf16

@@ -451,6 +451,7 @@ int g_num_cu = 0;
 
 int dadd_init_igemm() {
   int rc = dadd_init_igemm_dma();
+  if (rc == DADD_OK) rc = dadd_init_igemm_ups_fold();
   if (rc == DADD_OK) rc = dadd_init_conv_halo();
   if (rc == DADD_OK) rc = dadd_set_max_lds(REG_KERNELS);
   int dev = 0;
@@ -477,7 +478,7 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
   a.counters = d->counters;
   a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.C1 = d->C1; a.C2 = d->C2;
   a.Ho = d->Ho; a.Wo = d->Wo; a.N = d->N;
-  a.taps = d->taps; a.stride = d->stride; a.ups = d->ups; a.pad = d->pad;
+  a.taps = d->taps; a.stride = d->stride; a.ups = d->ups ? 1 : 0; a.pad = d->pad;   // (2, the fold, is decided below)
   a.flags = d->flags & (15 | DADD_TUNE_PERSIST | DADD_EPI_LNFOLD | DADD_EPI_ACT_MASK | DADD_EPI_GNSTAT | DADD_EPI_LNSTAT |
                         DADD_PRE_GN | DADD_PRE_GN_SILU | DADD_EPI_GNAPPLY | DADD_EPI_GNAPPLY_SILU);
   a.gno_out = static_cast<half_t*>(d->gn_out);
@@ -533,6 +534,24 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
 
   a.M = a.B * a.Ho * a.Wo;
   a.K = a.taps * Cin;
+  // The upsampled 3x3 as four 2x2 phase convs on pre-summed weights (dadd_hip.h DADD_TUNE_UPS_FOLD; igemm_ups_fold.hip).
+  // Operands the phase-ordered rows cannot address are refused; a request the mode does not take for its shape or
+  // tiling (split-K - the finish kernels index slabs by output row -, 64-row tiles, the register-staged kernel, a phase
+  // that is no whole number of 128-row tiles) runs the 9-tap gather on `w`, exactly as without the flag.
+  if ((d->flags & DADD_TUNE_UPS_FOLD) && d->w_fold != nullptr && a.ups) {
+    DADD_REQUIRE(a.C2 == 0 && !geglu && !(a.flags & (DADD_EPI_ROWVEC | DADD_EPI_RESIDUAL | DADD_EPI_LNSTAT | DADD_EPI_GNAPPLY)),
+                 "igemm: the folded upsample conv takes one source and a bias / activation / GNSTAT epilogue "
+                 "(no x2, rowvec, residual, GEGLU, LNSTAT, GNAPPLY)");
+    DADD_REQUIRE(dadd_aligned16(d->w_fold), "igemm: pointers must be 16-byte aligned");
+    const long long rows = (long long)a.B * a.Hi * a.Wi;
+    if (d->splitk <= 1 && (d->tile_m == 0 || d->tile_m == 128) && !(d->flags & DADD_TUNE_NODMA) && a.pad == 1 &&
+        a.Ho == 2 * a.Hi && a.Wo == 2 * a.Wi && rows % 128 == 0 &&
+        (!(a.flags & DADD_EPI_GNSTAT) || (a.Hi * a.Wi) % 64 == 0) && (size_t)a.N * 4 * Cin * 2 * 4 < 0x7FF00000ull) {
+      a.ups = 2;
+      a.w = static_cast<const half_t*>(d->w_fold);
+      a.K = 4 * Cin;
+    }
+  }
   a.nkt = a.K / BK;
   int tile_n = d->tile_n;
   if (geglu) {
@@ -608,8 +627,8 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
             (size_t)a.mtiles * a.ntiles < DADD_FASTDIV_MAX;
   a.plain = a.taps == 1 && a.stride == 1 && a.pad == 0 && !a.ups && a.Ho == a.Hi && a.Wo == a.Wi;
   if (a.fd_on) {
-    a.fd_howo = dadd_fastdiv_make((uint32_t)(a.Ho * a.Wo));
-    a.fd_wo = dadd_fastdiv_make((uint32_t)a.Wo);
+    a.fd_howo = dadd_fastdiv_make((uint32_t)(a.ups == 2 ? a.Hi * a.Wi : a.Ho * a.Wo));      // (ups_fold_decode)
+    a.fd_wo = dadd_fastdiv_make((uint32_t)(a.ups == 2 ? a.Wi : a.Wo));
     a.fd_cin = dadd_fastdiv_make((uint32_t)Cin);
     a.ngn = 1;
     a.fd_t1 = a.fd_t2 = dadd_fastdiv_make(1);
@@ -699,7 +718,7 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
   // Run-ahead weight prefetch of igemm_dma.hip (igemm_args.h): the first DADD_PF_KTILES weight tiles of a K slice, where
   // at least DADD_PF_MIN_SHARE row-tile workgroups share the strip and split its lines between them.  Not on the
   // persistent ring, whose workgroups walk runs of tiles, and not on the halo conv (measured: no gain there).
-  a.pf_kt = (dma && !halo && a.korder == 0 && !out->persistent && a.mtiles >= DADD_PF_MIN_SHARE)
+  a.pf_kt = (dma && !halo && a.korder == 0 && !out->persistent && (a.ups == 2 ? a.mtiles / 4 : a.mtiles) >= DADD_PF_MIN_SHARE)
                 ? (a.kps < DADD_PF_KTILES ? a.kps : DADD_PF_KTILES) : 0;
   if (halo) {
     DADD_REQUIRE(window, "conv_halo: operand larger than the 2 GiB buffer window");
@@ -712,7 +731,8 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out) {
     // how a folded LayerNorm gets its row statistics (LNK, igemm_dma.hip): 1 the kernel sums the rows itself, 2 (128-row
     // tiles) the producer's partials staged in LDS, 0 no fold or the epilogue reads the partials from global memory
     const int lnk = (a.ups || !(a.flags & DADD_EPI_LNFOLD)) ? 0 : (a.ln_stats_in == nullptr ? 1 : (tile_m == 128 ? 2 : 0));
-    out->main = dadd_igemm_dma_row(tile_m, tile_n, !out->persistent && tile_m == 128 && a.ups, out->persistent, lnk);
+    out->main = a.ups == 2 ? dadd_igemm_ups_fold_row(tile_m, tile_n)
+                           : dadd_igemm_dma_row(tile_m, tile_n, !out->persistent && tile_m == 128 && a.ups, out->persistent, lnk);
   } else {
     out->main = dadd_find_row(REG_KERNELS, tile_m, tile_n, deep && !(tile_m == 128 && tile_n == 160));
   }

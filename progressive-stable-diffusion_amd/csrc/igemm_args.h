@@ -32,7 +32,7 @@ struct IgemmArgs {
   const float* gno_beta;
   float gno_eps;
   int B, Hi, Wi, C1, C2, Ho, Wo, N;
-  int taps, stride, ups, pad;
+  int taps, stride, ups, pad;   // ups: 0, 1 (9-tap gather on the virtual 2Hi x 2Wi image) or 2 (four phase convs, w = the folded weights)
   int ldo, ldr, ld_rowvec;
   int splitk, flags;
   int M, K, nkt, kps, ntiles;
@@ -97,6 +97,16 @@ __device__ __forceinline__ void row_decode(const IgemmArgs& p, int m, int HoWo, 
   const int rem = m - b * HoWo;
   oy = p.fd_on ? (int)dadd_fastdiv_div((uint32_t)rem, p.fd_wo) : rem / p.Wo;
   ox = rem - oy * p.Wo;
+}
+
+// DADD_TUNE_UPS_FOLD (igemm_ups_fold.hip; igemm_dma_kernel.h UPS = 2): row r of a phase -> input pixel (sample, y, x).  In that mode fd_howo and
+// fd_wo divide by Hi*Wi and Wi.
+__device__ __forceinline__ void ups_fold_decode(const IgemmArgs& p, int r, int& b, int& y, int& x) {
+  const int HiWi = p.Hi * p.Wi;
+  b = p.fd_on ? (int)dadd_fastdiv_div((uint32_t)r, p.fd_howo) : r / HiWi;
+  const int rem = r - b * HiWi;
+  y = p.fd_on ? (int)dadd_fastdiv_div((uint32_t)rem, p.fd_wo) : rem / p.Wi;
+  x = rem - y * p.Wi;
 }
 
 // XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (id % 8 shares an XCD, each
@@ -176,11 +186,12 @@ __device__ __forceinline__ void tile_decode_fast(const IgemmArgs& p, int tile_id
   }
 }
 
-// algorithmic work of one implicit-GEMM launch (roofline columns of the profiling records)
+// work of one implicit-GEMM launch as executed (roofline columns of the profiling records): the folded upsample conv
+// (a.ups == 2) counts its K = 4 Cin, the MFMAs it runs, not the 9 taps of the conv it replaces
 static inline double dadd_igemm_flop(const IgemmArgs& a) { return 2.0 * (double)a.M * (double)a.N * (double)a.K; }
 static inline double dadd_igemm_bytes(const IgemmArgs& a) {
   const double n_out = (a.flags & DADD_EPI_GEGLU) ? a.N / 2 : a.N;
-  return 2.0 * ((double)a.B * a.Hi * a.Wi * (a.C1 + a.C2) + (double)a.N * a.K + (double)a.M * n_out +
+  return 2.0 * ((double)a.B * a.Hi * a.Wi * (a.C1 + a.C2) + (double)a.N * a.K * (a.ups == 2 ? 4.0 : 1.0) + (double)a.M * n_out +
                 ((a.flags & DADD_EPI_RESIDUAL) ? (double)a.M * a.N : 0.0));
 }
 
@@ -214,7 +225,7 @@ __device__ __forceinline__ void ln_finish(float (&s1)[MI], float (&s2)[MI], int 
 }
 
 // ---- kernel table, resolve, launch ------------------------------------------------------------------------------
-// Every kernel instantiation of igemm.hip, igemm_dma.hip and conv_halo.hip is ONE row of its file's table: the name
+// Every kernel instantiation of igemm.hip, igemm_dma.hip, igemm_ups_fold.hip and conv_halo.hip is ONE row of its file's table: the name
 // the profiler shows, the kernel, threads per block, dynamic LDS bytes, and the template arguments it was made from
 // (`targ`, the lookup key).  The row macros build the name from the same arguments as the template-id.  dadd_init_*
 // loops over a table for the LDS attribute; dadd_igemm_resolve (igemm.hip) picks rows; nothing else names a kernel.
@@ -257,6 +268,8 @@ int dadd_igemm_resolve(const dadd_igemm_desc* d, int num_cu, IgemmLaunch* out);
 
 int dadd_init_igemm_dma();
 const IgemmKernel* dadd_igemm_dma_row(int tile_m, int tile_n, bool ups, bool persistent, int lnk);
+int dadd_init_igemm_ups_fold();
+const IgemmKernel* dadd_igemm_ups_fold_row(int tile_m, int tile_n);
 int dadd_init_conv_halo();
 bool dadd_conv_halo_applicable(const IgemmArgs& a, int tile_n);
 int dadd_conv_halo_gn_channels(int Wo);

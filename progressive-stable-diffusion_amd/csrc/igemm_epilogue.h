@@ -209,12 +209,22 @@ __device__ __forceinline__ float dadd_row16_sum(float v) {
   return v;
 }
 
+// The folded upsample conv (UPSF; igemm_ups_fold.hip, 128-row tiles): row `row` of the tile at m0 is input pixel
+// (b, y, x) of phase (m0 / BM) & 3 = 2 py + px and is stored at output pixel (2y + py, 2x + px).  -> that pixel's row of `out`
+template <int BM>
+__device__ __forceinline__ size_t epi_fold_row(const IgemmArgs& p, int m0, int row) {
+  const int mt = m0 / BM;
+  int b, y, x;
+  ups_fold_decode(p, (mt >> 2) * BM + row, b, y, x);
+  return ((size_t)(b * p.Ho + 2 * y + ((mt >> 1) & 1))) * p.Wo + 2 * x + (mt & 1);
+}
+
 // Every path but GEGLU and the GroupNorm statistics.  FOLD: EPI_PLAIN (also DADD_EPI_LNSTAT), or the LayerNorm folded
 // with c1 and the composed bias taken from global memory (EPI_FOLD_GLOBAL: 64-row tiles, whose MFMA waves wait on the
 // LDS fill anyway) or staged in LDS at ln_cb (EPI_FOLD_LDS).  The folded linears (qkv, attn2.to_q, the CLIP / resampler
 // blocks) have no row partials to write.
 enum { EPI_PLAIN = 0, EPI_FOLD_GLOBAL = 1, EPI_FOLD_LDS = 2 };
-template <int J, int MI, int WM, int WN, int MODE, int FOLD>
+template <int J, int MI, int WM, int WN, int MODE, int FOLD, bool UPSF = false>
 __device__ __forceinline__ void epi_tile(const IgemmArgs& p, f4 (&acc)[J][MI], int m0, int n0, int wm, int wn, int g, int mc,
                                          int HoWo, const float (&lmu)[MI], const float (&lrs)[MI], const char* ln_cb) {
   const bool lnstat = FOLD == EPI_PLAIN && (p.flags & DADD_EPI_LNSTAT) != 0 && n0 + wn * WN < p.N;
@@ -224,6 +234,11 @@ __device__ __forceinline__ void epi_tile(const IgemmArgs& p, f4 (&acc)[J][MI], i
   float rs1[MI], rs2[MI];      // DADD_EPI_LNSTAT: this lane's share of row m (J x 4 columns)
 #pragma unroll
   for (int i = 0; i < MI; ++i) rs1[i] = rs2[i] = 0.f;
+  [[maybe_unused]] size_t orow[MI];      // UPSF: where row fragment i is stored
+  if constexpr (UPSF) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i) orow[i] = epi_fold_row<2 * WM>(p, m0, wm * WM + i * 16 + mc);
+  }
   epi_for_each<J, MI, MODE>(
       [&](int o) __attribute__((always_inline)) { ops.batch(p, o, HoWo); },
       [&](int i, int j) __attribute__((always_inline)) {
@@ -252,7 +267,8 @@ __device__ __forceinline__ void epi_tile(const IgemmArgs& p, f4 (&acc)[J][MI], i
             rs2[i] = fmaf(f, f, rs2[i]);
           }
         }
-        *reinterpret_cast<h4*>(p.out + (size_t)m * p.ldo + n) = o;
+        if constexpr (UPSF) *reinterpret_cast<h4*>(p.out + orow[i] * p.ldo + n) = o;
+        else *reinterpret_cast<h4*>(p.out + (size_t)m * p.ldo + n) = o;
       },
       [&](int i) __attribute__((always_inline)) {
         const int m = m0 + wm * WM + i * 16 + mc;
@@ -270,7 +286,8 @@ __device__ __forceinline__ void epi_tile(const IgemmArgs& p, f4 (&acc)[J][MI], i
 // `gn_scratch`: 4 KB of LDS (4 MFMA waves x [80 columns][2] floats) that no LDS-DMA can still be writing when the
 // epilogue runs — the staging area of the GroupNorm statistics (DADD_EPI_GNSTAT).
 // MODE: EPI_TILE / EPI_ROWS / EPI_COLS above.
-template <int J, int MI, int WM, int WN, int MODE = EPI_TILE>
+// UPSF: the folded upsample conv - rows are stored at epi_fold_row (bias, activation and DADD_EPI_GNSTAT only: resolve).
+template <int J, int MI, int WM, int WN, int MODE = EPI_TILE, bool UPSF = false>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][MI], int m0, int n0,
                                                int wm, int wn, int lane, int z, char* smem,
                                                const float* ln_mu = nullptr, const float* ln_rs = nullptr,
@@ -330,7 +347,17 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
     // Sums are taken over the ROUNDED fp16 values (what the consumer reads), in a fixed order: bit-reproducible.
     float* scratch = reinterpret_cast<float*>(gn_scratch) + (wm * 2 + wn) * 256;   // [WN <= 80][2] per wave
     const int mrow0 = m0 + wm * WM;
-    const int bsmp = row_sample(p, mrow0, HoWo);
+    // UPSF: the wave's WM rows are input pixels r0 .. r0 + WM of one phase and (Hi*Wi % WM == 0) one sample; they form chunk
+    // phase * (Hi*Wi / WM) + (block inside the sample) of its Ho*Wo / WM chunks
+    [[maybe_unused]] const int fold_r0 = ((m0 / (2 * WM)) >> 2) * (2 * WM) + wm * WM, fold_ph = (m0 / (2 * WM)) & 3;
+    int bsmp;
+    if constexpr (UPSF) bsmp = p.fd_on ? (int)dadd_fastdiv_div((uint32_t)fold_r0, p.fd_howo) : fold_r0 / (p.Hi * p.Wi);
+    else bsmp = row_sample(p, mrow0, HoWo);
+    [[maybe_unused]] size_t orow[MI];
+    if constexpr (UPSF) {
+#pragma unroll
+      for (int i = 0; i < MI; ++i) orow[i] = epi_fold_row<2 * WM>(p, m0, wm * WM + i * 16 + mc);
+    }
     const bool has_bias = (p.flags & DADD_EPI_BIAS) != 0, has_rv = (p.flags & DADD_EPI_ROWVEC) != 0;
     const bool has_res = (p.flags & DADD_EPI_RESIDUAL) != 0;
     // the operands of the column blocks (full tiles: nothing to clamp): EPI_TILE all blocks ahead of the first store,
@@ -386,7 +413,8 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
           cs[r] += f;
           cq[r] = fmaf(f, f, cq[r]);
         }
-        *reinterpret_cast<h4*>(p.out + (size_t)m * p.ldo + n) = o;
+        if constexpr (UPSF) *reinterpret_cast<h4*>(p.out + orow[i] * p.ldo + n) = o;
+        else *reinterpret_cast<h4*>(p.out + (size_t)m * p.ldo + n) = o;
       }
       // 16 lanes (mc) share a column quad: butterfly inside the DPP row (quad perms, half mirror, mirror)
 #pragma unroll
@@ -412,7 +440,9 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
         a += scratch[(lane * p.gn_cg + c) * 2];
         q += scratch[(lane * p.gn_cg + c) * 2 + 1];
       }
-      const int chunk = (mrow0 - bsmp * HoWo) / WM;
+      int chunk;
+      if constexpr (UPSF) chunk = (fold_ph * (p.Hi * p.Wi) + fold_r0 - bsmp * (p.Hi * p.Wi)) / WM;
+      else chunk = (mrow0 - bsmp * HoWo) / WM;
       const int grp = (n0 + wn * WN) / p.gn_cg + lane;
       float* w = p.gn_ws + (((size_t)bsmp * p.gn_nchunk + chunk) * 32 + grp) * 2;
       w[0] = a;
@@ -563,6 +593,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f4 (&acc)[J][
       if (fold) geglu(std::true_type{});
       else geglu(std::false_type{});
     }
+    return;
+  }
+  if constexpr (UPSF) {
+    epi_tile<J, MI, WM, WN, MODE, EPI_PLAIN, true>(p, acc, m0, n0, wm, wn, g, mc, HoWo, lmu, lrs, ln_cb);
     return;
   }
   if (lds_fold) epi_tile<J, MI, WM, WN, MODE, EPI_FOLD_LDS>(p, acc, m0, n0, wm, wn, g, mc, HoWo, lmu, lrs, ln_cb);

@@ -87,6 +87,25 @@ def fold_layernorm(w: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tens
     return w16, w16.double().sum(dim=1).float(), bias.float()
 
 
+def fold_ups_weight(w9: torch.Tensor) -> torch.Tensor:
+    """Packed 3x3 weight ``[N][9*Cin]`` (``pack_conv``) of a "nearest 2x upsample -> conv3x3" -> ``[4][N][4*Cin]``: the
+    four 2x2 phase convs on the un-upsampled input that compute the same thing (csrc/igemm_ups_fold.hip).  Output
+    pixel (2y + py, 2x + px) reads input rows y + py - 1 + dy, dy in {0, 1}; the nine taps collapse onto them as
+    py = 0: {ky 0} | {ky 1, 2}, py = 1: {ky 0, 1} | {ky 2}, columns alike.  Phase = 2 py + px, taps in (dy, dx) order.
+    Every entry is the sum of 1, 2 or 4 of the 16-bit weights, taken in float64 and rounded ONCE to the weight's type
+    (as ``grad_ops.dgrad_weight_ups`` does for the backward)."""
+    n, cin = w9.shape[0], w9.shape[1] // 9
+    assert w9.dim() == 2 and w9.shape[1] == 9 * cin
+    w = w9.reshape(n, 3, 3, cin).double()
+    sets = (((0,), (1, 2)), ((0, 1), (2,)))                      # [parity][d] -> the ky (kx) summed
+    phases = []
+    for py in range(2):
+        for px in range(2):
+            taps = [w[:, list(sets[py][dy])][:, :, list(sets[px][dx])].sum((1, 2)) for dy in range(2) for dx in range(2)]
+            phases.append(torch.stack(taps, 1).reshape(n, 4 * cin))
+    return torch.stack(phases, 0).to(w9.dtype).contiguous()
+
+
 def lds_image(w: torch.Tensor) -> torch.Tensor:
     """[R, 64] fp16 slab -> the LDS image the DMA kernels read fragments from: 128-byte rows, the eight 16-byte chunks
     of row r stored at position ``chunk ^ ((r >> 1) & 7)`` (csrc/igemm_dma.hip ``lds_off``; an involution)."""
@@ -165,6 +184,29 @@ WEIGHT_PREFETCH_MIN_BYTES = 2 * 1024 * 1024
 GN_FROM_EPILOGUE = True
 GN_FUSED_MAX_BYTES = 16 * 1024       # csrc/norm.hip: below this slab size the single-launch LDS GroupNorm runs
 SPLITK_GN_ROWS = 16                  # rows per block / per GroupNorm chunk of splitk_finish_gn_kernel (16 or 64)
+
+
+# "Nearest 2x upsample -> conv3x3" as four 2x2 phase convs on pre-summed weights (fold_ups_weight, DADD_TUNE_UPS_FOLD):
+# K = 4 Cin instead of 9 Cin, 2.25x fewer MFMAs.  The folded copy is built once per plan, beside the packed weight.
+# Sites the split-K rule serves (the 8x8 -> 16x16 conv of the UNet: 256 rows per phase, weight-stream-bound) stay on
+# the gather kernel; False is the A/B switch.
+UPS_FOLD = True
+
+
+def ups_fold_tiling(m: int, n: int, cin: int) -> Optional[Tuple[int, int, int, int]]:
+    """(tile_m, tile_n, 1, tune | TUNE_UPS_FOLD) of an upsample conv that runs as four phase convs, None where it stays
+    on the gather: a table entry under the fold's own key (K = 4 Cin) decides; without one the fold runs where the
+    gather needs no K slices and every phase has whole 128-row tiles."""
+    if not UPS_FOLD:
+        return None
+    key = tiling_key(m, n, 4 * cin, 9, False, False, 1, 1)
+    hit = TILING_OVERRIDE.get(key) or TILING_TABLE.get(key)
+    if hit is not None:
+        return tuple(hit) if hit[3] & L.TUNE_UPS_FOLD else None
+    tile_m, tile_n, sk, tune = plan_tiling(m, n, 9 * cin, 9, False, False, 1, 1)
+    if sk != 1 or tile_m != 128 or (m // 4) % 128 or (tune & L.TUNE_NODMA):
+        return None
+    return tile_m, tile_n, 1, tune | L.TUNE_UPS_FOLD
 
 
 # LayerNorm folded into the consuming linear (qkv, attn2.to_q, GEGLU projection) instead of a LayerNorm launch and a
@@ -394,6 +436,15 @@ class _Plan:
         return self.cached((self.prefix + key, pack.__name__),
                            lambda: self.be.to_device(pack(self.sd[self.prefix + key], self.dtype)))
 
+    def ups_fold(self, w9):
+        """The folded copy ``[4][N][4 Cin]`` of the packed upsample-conv weight ``w9``, kept as long as ``w9`` (same cache,
+        same ``keep``) and registered with a backend that runs the phase convs (``register_ups_fold``); others ignore
+        DADD_TUNE_UPS_FOLD and run the 9-tap gather."""
+        w4 = self.cached(("ups_fold", w9.data_ptr()), lambda: self.be.to_device(fold_ups_weight(w9.cpu())))
+        if hasattr(self.be, "register_ups_fold"):
+            self.be.register_ups_fold(w9, w4)
+        return w4
+
     def f(self, key):
         return self.cached((self.prefix + key, "f32"), lambda: self.be.to_device(self.sd[self.prefix + key].float()))
 
@@ -431,6 +482,10 @@ class _Plan:
         m = out_shape[0] * out_shape[1] * out_shape[2]
         tile_m, tile_n, sk, tune = plan_tiling(m, n, w.shape[1], taps, bool(flags & L.EPI_GEGLU), residual is not None,
                                                ups, stride)
+        fold = ups_fold_tiling(m, n, w.shape[1] // 9) if ups and x2 is None and residual is None and rowvec is None else None
+        if fold is not None:
+            tile_m, tile_n, sk, tune = fold
+            self.ups_fold(w)
         if taps == 9 and HALO_DUO:
             tune |= L.TUNE_SHALLOW
         if ln_c1 is not None:

@@ -20,6 +20,8 @@ _SINGLE_SOURCES = ("attn2_fused", "ffn_block", "tf_head", "conditioning", "api",
 _TWINNED_SOURCES = (
     # the UNet's generic-path kernels
     "igemm", "igemm_dma", "conv_halo", "norm", "attention", "elementwise",
+    # the upsample convs as four 2x2 phase convs on pre-summed weights (the LDS-DMA ring of igemm_dma_kernel.h, K = 4 Cin)
+    "igemm_ups_fold",
     # training backward: the M-reduction GEMM of the weight gradient
     "wgrad",
     # training backward: GroupNorm(+SiLU) / LayerNorm / GEGLU and the plain GEGLU forward
@@ -44,6 +46,7 @@ EPI_LNFOLD, EPI_QUICKGELU, EPI_GELU, EPI_SIGMOID, EPI_GNSTAT, EPI_LNSTAT = 128, 
 PRE_GN, PRE_GN_SILU = 8192, 16384
 EPI_GNAPPLY, EPI_GNAPPLY_SILU = 32768, 65536
 TUNE_SHALLOW, TUNE_NODMA, TUNE_PERSIST = 16, 32, 64
+TUNE_UPS_FOLD = 131072
 XATTN_SPLIT, XATTN_BASELINE = 0, 1
 DGRAD_STRIDE2, DGRAD_UPS = 0, 1
 END_WGRAD_IN, END_WGRAD_OUT = 0, 1
@@ -61,7 +64,8 @@ class IgemmDesc(C.Structure):
                                                            ("ln_stats_out", vp), ("ln_stats_in", vp), ("ln_parts_out", i32), ("ln_parts_in", i32),
                                                            ("gn_in_ws", vp), ("gn_in_gamma", vp), ("gn_in_beta", vp), ("gn_in_nchunk", i32), ("gn_in_eps", f32),
                                                            ("gn_in_ws2", vp), ("gn_in_nchunk2", i32),
-                                                           ("gn_out", vp), ("gn_out_gamma", vp), ("gn_out_beta", vp), ("gn_out_eps", f32)]
+                                                           ("gn_out", vp), ("gn_out_gamma", vp), ("gn_out_beta", vp), ("gn_out_eps", f32),
+                                                           ("w_fold", vp)]
 
 
 class IgemmChoice(C.Structure):
