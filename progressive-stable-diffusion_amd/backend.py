@@ -835,6 +835,24 @@ class HipBackend:
                              f"got {tuple(table.shape)} {table.dtype}, n_tiles {n_tiles}")
         L.check(fn(_p(src), src.numel(), _p(dst), dst.numel(), _p(table), int(n_desc), int(n_tiles), self.s))
 
+    def plan_refresh(self, src, table, n_desc, n_wgs, dtype=torch.float16):
+        """One launch (csrc/plan_refresh.hip): from the flat fp32 ``src`` (the arena's ``p`` or ``ema``) into the
+        destinations the descriptors of ``table`` point to, for each what its packer in ``engine`` gives.  ``table``: the
+        device copy (int32 words) of an array of ``lib.PlanRefreshDesc`` that ``dadd_plan_refresh_plan`` has checked;
+        ``n_wgs`` its return value; ``dtype`` the 16-bit type of the table's destinations.  ``optim.PlanRefresh`` is the
+        owner of the tables."""
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"plan_refresh: destinations are fp16 or bf16, not {dtype}")
+        fn = getattr(self.lib, "dadd_plan_refresh_" + ("bf16" if dtype == torch.bfloat16 else "f16"))
+        words = C.sizeof(L.PlanRefreshDesc) // 4
+        if src.dtype != torch.float32 or src.dim() != 1 or not src.is_contiguous():
+            raise ValueError(f"plan_refresh: src must be a flat contiguous fp32 tensor, got {tuple(src.shape)} {src.dtype}")
+        if table.dtype != torch.int32 or table.dim() != 1 or not table.is_contiguous() or table.numel() != n_desc * words \
+                or n_desc < 1 or n_wgs < 1:
+            raise ValueError(f"plan_refresh: table must be {n_desc} x {words} contiguous int32 words and n_wgs positive, "
+                             f"got {tuple(table.shape)} {table.dtype}, n_wgs {n_wgs}")
+        L.check(fn(_p(src), src.numel(), _p(table), int(n_desc), int(n_wgs), self.s))
+
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""
         b, n, c3 = qkv.shape

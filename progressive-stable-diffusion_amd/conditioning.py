@@ -22,7 +22,7 @@ from typing import Dict, Iterator, Optional
 import torch
 
 from . import lib as L
-from .engine import fold_layernorm, plan_tiling
+from .engine import Recipe, fold_layernorm, plan_tiling
 
 F16, F32 = torch.float16, torch.float32
 
@@ -41,6 +41,12 @@ class _Params:
         if not self.p:
             raise KeyError(f"no parameters under '{prefix}.' in the state dict")
         self._packed: Dict = {}
+        # where every device tensor came from (engine.Recipe): the masters are refreshed in place, every packed tensor
+        # that exists is written again by optim.PlanRefresh; a packed tensor without a recipe lands in ``unrefreshable``
+        self.prefix = prefix
+        self.frozen = False
+        self.recipes = [Recipe("copy32", (prefix + "." + k,), (t,)) for k, t in self.p.items()]
+        self.unrefreshable = []
 
     def parameters(self) -> Iterator[torch.Tensor]:
         return iter(self.p.values())
@@ -49,14 +55,21 @@ class _Params:
         return self
 
     # ---- packing (once per module) -----------------------------------------------------------------------------
-    def pk(self, key, make):
+    def pk(self, key, make, recipe=None):
+        """``recipe``: ``value -> [Recipe, ...]`` for what ``make()`` returns."""
         t = self._packed.get(key)
         if t is None:
             t = self._packed[key] = make()
+            if not self.frozen:
+                if recipe is None:
+                    self.unrefreshable.append(key)
+                else:
+                    self.recipes += recipe(t)
         return t
 
     def w16(self, key):
-        return self.pk(("w", key), lambda: self.p[key + ".weight"].to(F16).contiguous())
+        return self.pk(("w", key), lambda: self.p[key + ".weight"].to(F16).contiguous(),
+                       lambda t: [Recipe("cast", (f"{self.prefix}.{key}.weight",), (t,))])
 
     def b32(self, key):
         return self.p.get(key + ".bias")
@@ -68,7 +81,9 @@ class _Params:
             b = torch.cat([self.p[k] for k in bkeys]).cpu() if bkeys else None
             w16, c1, bias = fold_layernorm(w, b, self.p[norm + ".weight"].cpu(), self.p[norm + ".bias"].cpu())
             return tuple(self.be.to_device(t.contiguous()) for t in (w16, c1, bias))
-        return self.pk(("fold", name), make)
+        u = self.prefix + "."
+        return self.pk(("fold", name), make, lambda t: [Recipe("lnfold", (
+            [u + k for k in wkeys], [u + k for k in bkeys] if bkeys else None, u + norm + ".weight", u + norm + ".bias"), t)])
 
     # ---- ops ---------------------------------------------------------------------------------------------------
     def rows16(self, x: torch.Tensor) -> torch.Tensor:
@@ -111,9 +126,13 @@ class _Params:
                     w16, c1, bias = fold_layernorm(self.p[wk][lo:hi].cpu(), self.p[bk][lo:hi].cpu(),
                                                    self.p[norm + ".weight"].cpu(), self.p[norm + ".bias"].cpu())
                     return tuple(self.be.to_device(t.contiguous()) for t in (w16, c1, bias))
-                return self.pk(("mha", key, name), make)
+                u = self.prefix + "."
+                return self.pk(("mha", key, name), make, lambda t: [Recipe("lnfold", (
+                    [(u + wk, lo, hi)], [(u + bk, lo, hi)], u + norm + ".weight", u + norm + ".bias"), t)])
+            # (the bias is a view of the master: refreshed with it)
             return self.pk(("mha", key, name), lambda: (self.p[wk][lo:hi].to(F16).contiguous(), None,
-                                                        self.p[bk][lo:hi].contiguous()))
+                                                        self.p[bk][lo:hi].contiguous()),
+                           lambda t: [Recipe("cast", ((self.prefix + "." + wk, lo, hi),), (t[0],))])
         wq, cq, bq_ = split(0, e, q_norm, "q")
         wkv, ckv, bkv = split(e, 3 * e, kv_norm, "kv")
         q = self.gemm(q_rows, wq, bq_, ln_c1=cq)
@@ -292,6 +311,7 @@ class ImageEncoder(_Params):
 
     def __init__(self, sd, device, clip_config: Optional[dict] = None, prefix="image_encoder.image_encoder", be=None):
         super().__init__(sd, prefix, device, be)
+        self.frozen, self.recipes = True, []         # the CLIP tower is frozen: nothing refreshes it
         cfg = dict(clip_config or clip_config_from_state_dict({k: v for k, v in self.p.items()}))
         self.cfg = cfg
         self.hidden_size, self.projection_dim = cfg["hidden_size"], cfg["projection_dim"]

@@ -47,6 +47,7 @@
 #define rowvec_grad_kernel rowvec_grad_kernel_bf16
 #define rowvec_grad_finish_kernel rowvec_grad_finish_kernel_bf16
 #define relayout_kernel relayout_kernel_bf16
+#define plan_refresh_kernel plan_refresh_kernel_bf16
 
 // host functions shared between the GEMM sources and with api.hip
 #define dadd_init_igemm dadd_init_igemm_bf16
@@ -103,3 +104,6 @@
 
 // C entry points (include/dadd_hip_relayout.h)
 #define dadd_dgrad_relayout_f16 dadd_dgrad_relayout_bf16
+
+// C entry points (include/dadd_hip_plan_refresh.h)
+#define dadd_plan_refresh_f16 dadd_plan_refresh_bf16

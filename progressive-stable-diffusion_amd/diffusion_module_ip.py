@@ -386,6 +386,8 @@ class DiffusionModuleWithIP:
         self.feature_purifier = (FeaturePurifier(state_dict, self.device, dc.purifier_num_heads, be=self.be)
                                  if dc.use_feature_purifier else None)
         self._unets: Dict[Tuple[int, int], OrdinalUNet] = {}
+        # set by training.Trainer.sync_module: the source synced last and the hook that refreshes a plan built afterwards
+        self._synced, self._plan_sync = None, None
         self._loops: Dict[Tuple[int, int], DdimLoop] = {}
         self.unet = self._unet_for(self.batch_size, self.latent_side)
         self.vae = SDVAE(self.be, state_dict, self.batch_size, self.latent_side, dc.latent_scale)
@@ -397,6 +399,8 @@ class DiffusionModuleWithIP:
             dc = self.diff_cfg
             plan = UNetPlan(self.be, self._sd, batch, side, use_routing_gates=dc.use_routing_gates,
                             use_frequency_strategy=dc.use_frequency_strategy, dtype=self.operand_dtype)
+            if self._plan_sync is not None:     # the live plans carry trained weights: this one must not be stale
+                self._plan_sync(plan)
             u = OrdinalUNet(plan, dc.use_routing_gates, self.cfg.model.conditioning_dim,
                             self.cfg.model.latent_channels, self.cfg.model.latent_channels)
             if self._unets:     # keep delta_scale consistent across plans

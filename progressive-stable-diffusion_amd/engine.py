@@ -160,6 +160,47 @@ def pack_head_stream(wp: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: t
     return torch.cat([p.reshape(-1) for p in pieces]).contiguous()
 
 
+class Recipe:
+    """Where a packed device tensor of a plan came from: the state-dict keys, the kind of packing and the destination
+    tensor(s) - what ``optim.PlanRefresh`` needs to write the tensor again from a flat array of fp32 masters
+    (csrc/plan_refresh.hip) without rebuilding the plan.  A source is a key or ``(key, lo, hi)``, a row slice.
+      ``copy32``       src: sources concatenated                        dst: (fp32 tensor,)              ``f()``, ``b_tp``
+      ``cast``         src: sources concatenated by rows                dst: (16-bit tensor,)            ``pack_conv``, qkv, kv
+      ``cast_cin8``    src: (key,)                                      dst: (16-bit [N][9][8],)         ``pack_conv_cin8``
+      ``geglu``        src: (weight, bias)                              dst: (16-bit weight, fp32 bias)  ``geglu_interleave``
+      ``lnfold``       src: (weights, biases or None, gamma, beta)      dst: (w16, c1, bias)             ``fold_layernorm``
+      ``upsfold``      src: (key,)                                      dst: (16-bit [4][N][4 Cin],)     ``fold_ups_weight``
+      ``head_stream``  src: (proj_in, to_q, to_k, to_v)                 dst: (stream,)                   ``pack_head_stream``
+      ``ffn_stream``   src: (ff.net.0.proj w, b, ff.net.2 w, proj_out)  dst: (stream, permuted bias)     ``pack_ffn_stream``
+    ``geglu``: an ``lnfold`` whose rows are in ``geglu_interleave``'s order."""
+    __slots__ = ("kind", "src", "dst", "geglu")
+    KINDS = ("copy32", "cast", "cast_cin8", "geglu", "lnfold", "upsfold", "head_stream", "ffn_stream")
+
+    def __init__(self, kind, src, dst, geglu=False):
+        assert kind in self.KINDS, kind
+        self.kind, self.src, self.dst, self.geglu = kind, tuple(src), tuple(dst), bool(geglu)
+
+    def keys(self):
+        """Every state-dict key the recipe reads."""
+        out = []
+
+        def walk(x):
+            if isinstance(x, str):
+                out.append(x)
+            elif isinstance(x, tuple) and len(x) == 3 and isinstance(x[0], str) and isinstance(x[1], int):
+                out.append(x[0])
+            elif x is not None:
+                for y in x:
+                    walk(y)
+        walk(self.src)
+        return out
+
+
+FROZEN = object()        # ``recipe=FROZEN``: an upload of something no training changes (routing gates)
+STAGED = object()        # ``recipe=STAGED``: an upload that only feeds a stacked copy; the copy carries the recipe
+_PACK_RECIPE = {"pack_conv": "cast", "pack_conv_cout4": "cast", "pack_conv_cin8": "cast_cin8"}
+
+
 # GroupNorm (+ SiLU) applied inside the consuming 3x3 conv (DADD_PRE_GN, csrc/conv_halo.hip GNIN): the halo is normalised
 # in LDS by the loader waves; needs the producer's chunk partials, one source, <= 1024 input channels, the halo kernel
 GN_IN_CONV = True
@@ -363,6 +404,12 @@ class _Plan:
         # on MI355X for these shapes (M=256 N=1280 K=11520, 16 slices: 122 us vs 27 us): every slice
         # pays an agent-scope release (L2 write-back) — cdna_hip_programming.md "cut GEMM->GEMM seams".
         self.sk_counters = None
+        # every device tensor derived from ``sd`` has a Recipe; an upload without one is listed in ``unrefreshable``.
+        # ``frozen`` plans (VAE) record neither: nothing trains their weights.
+        self.recipes: List[Recipe] = []
+        self.unrefreshable: List = []
+        self.frozen = False
+        self._src_key: Dict[int, str] = {}      # packed 3x3 weight -> its state-dict key (ups_fold)
 
     def rec(self, fn, *a, **k):
         self.ops.append((fn, a, k))
@@ -408,18 +455,26 @@ class _Plan:
         if inserts:
             self.ops.append((self.be.prefetch_join, (), {}))
 
-    def dev(self, t, dtype=None):
-        """A parameter or I/O buffer the plan uploads directly (not shared between plans)."""
+    def dev(self, t, dtype=None, recipe=None):
+        """A parameter or I/O buffer the plan uploads directly (not shared between plans).  ``recipe``: ``(kind, src)`` of
+        the ``Recipe`` that writes it again, ``FROZEN`` or ``STAGED``."""
         d = self.be.to_device(t, dtype)
         self.keep.append(d)
+        if recipe is not FROZEN and recipe is not STAGED and not self.frozen:
+            if recipe is None:
+                self.unrefreshable.append(("dev", tuple(d.shape), d.dtype))
+            else:
+                self.recipes.append(Recipe(recipe[0], recipe[1], (d,)))
         return d
 
-    def cached(self, key, make):
+    def cached(self, key, make, recipe=None):
         """Packed device tensor(s) for ``key``: ``make()`` uploads one tensor or a tuple (``be.to_device``) on the first
         request - of any plan that shares the optional cross-plan cache (``wcache``: plans for other batch sizes or tilings
         over the same state dict share the packed weights instead of re-packing 1.9 GB each).  The plan-local memo gives one
         entry per key (fuse_gn hints name the same tensors twice) and puts each tensor into ``keep`` once.  The key carries
-        the plan's dtype: fp16 and bf16 plans over one cache never hand each other their packed weights."""
+        the plan's dtype: fp16 and bf16 plans over one cache never hand each other their packed weights.
+        ``recipe``: ``value -> [Recipe, ...]`` for what ``make()`` returns, recorded by every plan that takes the entry (plans
+        over one ``wcache`` share destinations: a refresh writes each once)."""
         key = (*key, self.dtype)
         t = self._memo.get(key)
         if t is None:
@@ -430,23 +485,35 @@ class _Plan:
                     self.wcache[key] = t
             self._memo[key] = t
             self.keep += t if isinstance(t, tuple) else (t,)
+            if not self.frozen:
+                if recipe is None:
+                    self.unrefreshable.append(key)
+                else:
+                    self.recipes += recipe(t)
         return t
 
     def w(self, key, pack=pack_conv):
-        return self.cached((self.prefix + key, pack.__name__),
-                           lambda: self.be.to_device(pack(self.sd[self.prefix + key], self.dtype)))
+        full = self.prefix + key
+        t = self.cached((full, pack.__name__), lambda: self.be.to_device(pack(self.sd[full], self.dtype)),
+                        (lambda t: [Recipe(_PACK_RECIPE[pack.__name__], (full,), (t,))]) if pack.__name__ in _PACK_RECIPE else None)
+        self._src_key[t.data_ptr()] = full
+        return t
 
     def ups_fold(self, w9):
         """The folded copy ``[4][N][4 Cin]`` of the packed upsample-conv weight ``w9``, kept as long as ``w9`` (same cache,
         same ``keep``) and registered with a backend that runs the phase convs (``register_ups_fold``); others ignore
         DADD_TUNE_UPS_FOLD and run the 9-tap gather."""
-        w4 = self.cached(("ups_fold", w9.data_ptr()), lambda: self.be.to_device(fold_ups_weight(w9.cpu())))
+        src = self._src_key.get(w9.data_ptr())
+        w4 = self.cached(("ups_fold", w9.data_ptr()), lambda: self.be.to_device(fold_ups_weight(w9.cpu())),
+                         (lambda t: [Recipe("upsfold", (src,), (t,))]) if src is not None else None)
         if hasattr(self.be, "register_ups_fold"):
             self.be.register_ups_fold(w9, w4)
         return w4
 
     def f(self, key):
-        return self.cached((self.prefix + key, "f32"), lambda: self.be.to_device(self.sd[self.prefix + key].float()))
+        full = self.prefix + key
+        return self.cached((full, "f32"), lambda: self.be.to_device(self.sd[full].float()),
+                           lambda t: [Recipe("copy32", (full,), (t,))])
 
     def _gn_partials_for(self, out, nchunk, extra=0):
         """GroupNorm chunk partials [B][nchunk + extra][32][2] of ``out``, written by the launch that takes the returned
@@ -597,18 +664,20 @@ class UNetPlan(_Plan):
         self.gn_ws = be.empty((batch * L.GN_MAX_CHUNKS * GROUPS * 2,), F32)
         u = self.prefix
         # ---- time path: linear_1, linear_2, all 22 time_emb_proj concatenated
-        self.w_t1 = self.dev(sd[u + "time_embedding.linear_1.weight"], F16)
-        self.b_t1 = self.dev(sd[u + "time_embedding.linear_1.bias"])
-        self.w_t2 = self.dev(sd[u + "time_embedding.linear_2.weight"], F16)
-        self.b_t2 = self.dev(sd[u + "time_embedding.linear_2.bias"])
+        te = u + "time_embedding.linear_"
+        self.w_t1 = self.dev(sd[te + "1.weight"], F16, ("cast", (te + "1.weight",)))
+        self.b_t1 = self.dev(sd[te + "1.bias"], None, ("copy32", (te + "1.bias",)))
+        self.w_t2 = self.dev(sd[te + "2.weight"], F16, ("cast", (te + "2.weight",)))
+        self.b_t2 = self.dev(sd[te + "2.bias"], None, ("copy32", (te + "2.bias",)))
         names = self._resnet_names()
         self.temb_off, off = {}, 0
         for nme in names:
             self.temb_off[nme] = off
             off += sd[u + nme + ".time_emb_proj.weight"].shape[0]
         self.temb_cols = off
-        self.w_tp = self.dev(torch.cat([sd[u + n + ".time_emb_proj.weight"] for n in names]), F16)
-        self.b_tp = self.dev(torch.cat([sd[u + n + ".time_emb_proj.bias"] for n in names]))
+        tp_w, tp_b = [u + n + ".time_emb_proj.weight" for n in names], [u + n + ".time_emb_proj.bias" for n in names]
+        self.w_tp = self.dev(torch.cat([sd[k] for k in tp_w]), F16, ("cast", tp_w))
+        self.b_tp = self.dev(torch.cat([sd[k] for k in tp_b]), None, ("copy32", tp_b))
         self.temb_rows = be.zeros((batch, self.temb_cols), F32)     # current step's rows
         # ---- cross-attention conditioning caches (step invariant)
         self.sites = self._attn_sites()
@@ -616,19 +685,21 @@ class UNetPlan(_Plan):
         self.kv_w, self.kv, self.gates = {}, {}, {}
         for site, c in self.sites:
             ap = f"{u}{site}.transformer_blocks.0.attn2"
-            ws = [sd[ap + ".to_k.weight"], sd[ap + ".to_v.weight"]]
+            kv_keys = [ap + ".to_k.weight", ap + ".to_v.weight"]
             if use_routing_gates:
-                ws += [sd[ap + ".processor.to_k_dis.weight"], sd[ap + ".processor.to_v_dis.weight"]]
+                kv_keys += [ap + ".processor.to_k_dis.weight", ap + ".processor.to_v_dis.weight"]
                 self.gates[site] = self.dev(torch.stack([sd[ap + ".processor.anat_gate"],
-                                                         sd[ap + ".processor.dis_gate"]]).float())
+                                                         sd[ap + ".processor.dis_gate"]]).float(), None, FROZEN)
             else:
                 self.gates[site] = None
-            self.kv_w[site] = self.dev(torch.cat(ws), dtype)
+            self.kv_w[site] = self.dev(torch.cat([sd[k] for k in kv_keys]), dtype, ("cast", kv_keys))
             self.kv[site] = [be.zeros((batch, 1, self.T, self.kv_w[site].shape[0]), dtype)
                              for _ in range(2)]                     # [cond, uncond]
         self.cond16 = be.zeros((batch, 1, self.T, 768), dtype)
         self.kv_slot = 0
         self.cond_gen = 0      # advanced by every set_cond(): callers that cache projections key on it
+        self.weights_gen = 0   # advanced when the packed weights are rewritten in place (training.Trainer.sync_module):
+                               # what was computed FROM them and cached (DdimLoop's time-row table) keys on it
         # ---- attn2 folded into ONE kernel per block (dadd_attn2_fused_f16): with 16 keys per pathway
         # q K^T = x (W_q K^T) and P V W_o^T = P (V W_o^T), so the step-invariant conditioning absorbs both
         # projections.  Sites whose map is smaller than one 128-token tile (8x8) keep the three-kernel path.
@@ -641,7 +712,9 @@ class UNetPlan(_Plan):
                 if hw % 128 == 0 and c % 320 == 0 and batch * hw // 128 >= A2_MIN_TILES:
                     ap = f"{u}{site}.transformer_blocks.0.attn2"
                     self.a2[site] = dict(
-                        wq=self.dev(sd[ap + ".to_q.weight"].float()), wo=self.dev(sd[ap + ".to_out.0.weight"].float()),
+                        # (read once by _a2_group, which stacks them: the stacked copies are what a refresh rewrites)
+                        wq=self.dev(sd[ap + ".to_q.weight"].float(), None, STAGED),
+                        wo=self.dev(sd[ap + ".to_out.0.weight"].float(), None, STAGED),
                         mcat=be.zeros((batch, 384, c), F16), vw=be.zeros((batch, c, 384), F16),
                         # norm2 folded into the score GEMM (set by _transformer when the producer supplies row partials)
                         fold=False, ln_c1=be.zeros((batch, 384), F32), ln_d=be.zeros((batch, 384), F32),
@@ -675,6 +748,10 @@ class UNetPlan(_Plan):
                        mcat=be.zeros((ns, batch, 384, c), F16), vw=be.zeros((ns, batch, c, 384), F16),
                        ln_c1=be.zeros((ns, batch, 384), F32), ln_d=be.zeros((ns, batch, 384), F32))
         for i, n in enumerate(names):       # the per-site tensors the kernels read are slices of the stacked ones
+            tb = f"{self.prefix}{n}.transformer_blocks.0"
+            for key, src in (("wq", ".attn2.to_q.weight"), ("wo", ".attn2.to_out.0.weight"), ("gamma", ".norm2.weight"),
+                             ("beta", ".norm2.bias")):
+                self.recipes.append(Recipe("copy32", (tb + src,), (grp[key][i],)))      # the stacked copies
             for key in ("mcat", "vw", "ln_c1", "ln_d"):
                 self.a2[n][key] = grp[key][i]
             del self.a2[n]["wq"], self.a2[n]["wo"]
@@ -765,7 +842,9 @@ class UNetPlan(_Plan):
                 idx = geglu_interleave(torch.arange(w16.shape[0])[:, None].float(), torch.zeros(w16.shape[0]))[0][:, 0].long()
                 w16, c1, bias = w16[idx], c1[idx], bias[idx]
             return tuple(self.be.to_device(t.contiguous()) for t in (w16, c1, bias))
-        return self.cached((u + tb, "lnfold", name), make)
+        src = ([u + tb + k for k in wkey_list], [u + tb + bias_key] if bias_key else None, u + tb + norm + ".weight",
+               u + tb + norm + ".bias")
+        return self.cached((u + tb, "lnfold", name), make, lambda t: [Recipe("lnfold", src, t, geglu=geglu)])
 
     def _ln_then_linear(self, x, out_shape, fold, folded, plain, ln, flags=0):
         """The linear that consumes a LayerNorm of ``x``: folded into the GEMM where the policy says so (``fold``: row
@@ -804,7 +883,8 @@ class UNetPlan(_Plan):
         # attn1 (self)
         if fused_head:               # norm -> proj_in -> norm1 -> q|k|v in one launch (csrc/tf_head.hip)
             hstream = self.cached((u + tb, "head_stream"), lambda: self.be.to_device(pack_head_stream(
-                self.sd[u + site + ".proj_in.weight"], *[self.sd[u + tb + k] for k in qkv_keys])))
+                self.sd[u + site + ".proj_in.weight"], *[self.sd[u + tb + k] for k in qkv_keys])),
+                lambda t: [Recipe("head_stream", [u + site + ".proj_in.weight"] + [u + tb + k for k in qkv_keys], (t,))])
             hs = self.pool.get(shp)
             qkv = self.pool.get((b, h, w_, 3 * c))
             self.rec(self.be.tf_head, x.view(b, h * w_, c), hstream, xpart[0], xpart[1], self.f(site + ".norm.weight"),
@@ -819,7 +899,9 @@ class UNetPlan(_Plan):
             def _qkv():
                 return self.be.to_device(torch.cat([self.sd[u + tb + k] for k in qkv_keys]), self.dtype)
             qkv = self._ln_then_linear(hs, (b, h, w_, 3 * c), fold1, lambda: self._ln_linear(tb, ".norm1", "qkv", qkv_keys),
-                                       lambda: (self.cached((u + tb, "qkv"), _qkv), None), lambda: ln_of(hs, ".norm1"))
+                                       lambda: (self.cached((u + tb, "qkv"), _qkv, lambda t: [
+                                           Recipe("cast", [u + tb + k for k in qkv_keys], (t,))]), None),
+                                       lambda: ln_of(hs, ".norm1"))
         att = self.pool.get(shp)
         self.rec(self.be.self_attn, qkv.view(b, h * w_, 3 * c), att.view(b, h * w_, c), HEADS)
         self.pool.put(qkv)
@@ -858,7 +940,9 @@ class UNetPlan(_Plan):
                 st, b1p = pack_ffn_stream(self.sd[u + tb + ".ff.net.0.proj.weight"], self.sd[u + tb + ".ff.net.0.proj.bias"],
                                           self.sd[u + tb + ".ff.net.2.weight"], self.sd[u + site + ".proj_out.weight"])
                 return self.be.to_device(st), self.be.to_device(b1p)
-            stream, b1p = self.cached((u + tb, "ffn_stream"), _tail)
+            stream, b1p = self.cached((u + tb, "ffn_stream"), _tail, lambda t: [Recipe("ffn_stream", (
+                u + tb + ".ff.net.0.proj.weight", u + tb + ".ff.net.0.proj.bias", u + tb + ".ff.net.2.weight",
+                u + site + ".proj_out.weight"), t)])
             out = self.pool.get(shp)
             nchunk = (h * w_) // 32
             gkw = {}
@@ -879,7 +963,9 @@ class UNetPlan(_Plan):
         ff = self._ln_then_linear(
             h3, (b, h, w_, 4 * c), fold3,
             lambda: self._ln_linear(tb, ".norm3", "geglu", [".ff.net.0.proj.weight"], ".ff.net.0.proj.bias", geglu=True),
-            lambda: self.cached((u + tb, "geglu"), _geglu), lambda: ln_of(h3, ".norm3"), flags=L.EPI_GEGLU)
+            lambda: self.cached((u + tb, "geglu"), _geglu, lambda t: [Recipe("geglu", (
+                u + tb + ".ff.net.0.proj.weight", u + tb + ".ff.net.0.proj.bias"), t)]),
+            lambda: ln_of(h3, ".norm3"), flags=L.EPI_GEGLU)
         self.pool.put(ln_box[0])
         h4 = self.conv(ff, self.w(tb + ".ff.net.2.weight"), shp, bias=self.f(tb + ".ff.net.2.bias"),
                        residual=h3, taps=1, pad=0)
@@ -1057,6 +1143,7 @@ class _VaePlan(_Plan):
 
     def __init__(self, be, sd, batch: int, side: int, prefix):
         super().__init__(be, sd=sd, prefix=prefix)
+        self.frozen = True               # nothing trains the VAE: no recipes
         self.B, self.S = batch, side
         self.gn_ws = be.empty((batch * L.GN_MAX_CHUNKS * GROUPS * 2,), F32)
 
@@ -1232,7 +1319,7 @@ class DdimLoop:
         ts = timesteps.detach()
         ts = (ts if ts.device.type == "cpu" else ts.cpu()).long()
         n = ts.shape[0]
-        key = (tuple(ts.tolist()), alphas_cumprod.data_ptr(), alphas_cumprod._version)
+        key = (tuple(ts.tolist()), alphas_cumprod.data_ptr(), alphas_cumprod._version, self.u.weights_gen)
         if key == self._prepared and n <= self.cap:
             self.nsteps = n
             return

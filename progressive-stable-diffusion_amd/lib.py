@@ -37,7 +37,9 @@ _TWINNED_SOURCES = (
     # training backward of the fp32 row path: linear_rows, aoe_interp and the EPI_ROWVEC row (only the last one is in the twin)
     "rows_grad",
     # training: one-launch re-layout of the 16-bit weights for the data gradients
-    "relayout")
+    "relayout",
+    # training -> inference: one-launch refresh of the packed weights of live plans from the fp32 masters
+    "plan_refresh")
 SOURCES = tuple(s + ".hip" for s in _SINGLE_SOURCES) + tuple(s + sfx for s in _TWINNED_SOURCES for sfx in (".hip", "_bf16.hip"))
 
 DADD_OK, DADD_EINVAL, DADD_EHIP, DADD_ESTATE = 0, -1, -2, -3
@@ -281,6 +283,26 @@ RELAYOUT_PROTOTYPES = _with_bf16({
     "dadd_dgrad_relayout_f16": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, vp]),
 })
 
+# include/dadd_hip_plan_refresh.h: the one-launch refresh of live plans' packed weights (csrc/plan_refresh.hip)
+(PLAN_REFRESH_COPY32, PLAN_REFRESH_CAST, PLAN_REFRESH_GEGLU_W, PLAN_REFRESH_GEGLU_B, PLAN_REFRESH_LNFOLD,
+ PLAN_REFRESH_UPSFOLD, PLAN_REFRESH_HEAD_STREAM, PLAN_REFRESH_FFN_STREAM, PLAN_REFRESH_FFN_BIAS) = range(9)
+PLAN_REFRESH_GEGLU = 1
+PLAN_REFRESH_GROUPS, PLAN_REFRESH_SCALARS, PLAN_REFRESH_ROWS = 1024, 2048, 4
+
+
+class PlanRefreshDesc(C.Structure):
+    """Mirror of ``dadd_plan_refresh_desc``."""
+    _fields_ = [("src_off", C.c_longlong * 4), ("dst", vp * 3), ("dst_room", C.c_longlong * 3)] + \
+               [(n, i32) for n in ("kind", "N", "K", "Cs", "flags", "wg0")] + [("reserved", i32 * 2)]
+
+
+# every symbol include/dadd_hip_plan_refresh.h declares
+PLAN_REFRESH_PROTOTYPES = _with_bf16({
+    "dadd_plan_refresh_wgs": (C.c_longlong, [C.c_int] * 5),
+    "dadd_plan_refresh_plan": (C.c_longlong, [C.POINTER(PlanRefreshDesc), C.c_int, C.c_longlong]),
+    "dadd_plan_refresh_f16": (C.c_int, [vp, C.c_longlong, vp, C.c_int, C.c_int, vp]),
+})
+
 # The registry: header under include/ -> the table of what it declares.  A new header is one entry here; load(), the
 # dependencies of build() and the symbol check of __graft_entry__.build() follow.
 HEADER_PROTOTYPES = {
@@ -295,6 +317,7 @@ HEADER_PROTOTYPES = {
     "dadd_hip_rows_grad.h": ROWS_GRAD_PROTOTYPES,
     "dadd_hip_optim.h": OPTIM_PROTOTYPES,
     "dadd_hip_relayout.h": RELAYOUT_PROTOTYPES,
+    "dadd_hip_plan_refresh.h": PLAN_REFRESH_PROTOTYPES,
 }
 ALL_PROTOTYPES = {}
 for _header, _table in HEADER_PROTOTYPES.items():

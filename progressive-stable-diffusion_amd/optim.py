@@ -12,6 +12,9 @@ diffusion_module_ip.py: UNet and ordinal embedder at ``lr``, image projection an
 ``DgradRelayout`` stands next to the arena: it owns the second 16-bit buffer that holds every weight in the layout its
 data gradient reads, refreshed from ``p16`` by one launch of csrc/relayout.hip after each optimizer step.
 
+``PlanRefresh`` goes the other way: it writes the packed weights of live inference plans again from the arena's fp32
+masters or their EMA, by one launch of csrc/plan_refresh.hip per 16-bit type.
+
 ``training.Trainer`` wires these into a training step; ``DiffusionModuleWithIP.configure_optimizers()`` itself still
 raises.
 """
@@ -267,6 +270,199 @@ class DgradRelayout:
     def prepared(self, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(w16, wt)`` of ``name``: the ``prepared=`` argument of the ``grad_ops`` products."""
         return self.w16(name), self.wt(name)
+
+
+PLAN_REFRESH_KINDS = {"COPY32": L.PLAN_REFRESH_COPY32, "CAST": L.PLAN_REFRESH_CAST, "GEGLU_W": L.PLAN_REFRESH_GEGLU_W,
+                      "GEGLU_B": L.PLAN_REFRESH_GEGLU_B, "LNFOLD": L.PLAN_REFRESH_LNFOLD, "UPSFOLD": L.PLAN_REFRESH_UPSFOLD,
+                      "HEAD_STREAM": L.PLAN_REFRESH_HEAD_STREAM, "FFN_STREAM": L.PLAN_REFRESH_FFN_STREAM,
+                      "FFN_BIAS": L.PLAN_REFRESH_FFN_BIAS}
+_PR_F32 = ("COPY32", "GEGLU_B", "FFN_BIAS")
+
+
+def plan_refresh_table(items: Sequence[dict], src_numel: int):
+    """The descriptor table of one refresh launch.  ``items``: dicts with ``kind`` (a key of ``PLAN_REFRESH_KINDS``),
+    ``N``, ``K``, ``Cs``, ``flags``, ``src`` (up to four element offsets into the flat fp32 source, -1 = absent) and
+    ``dst`` (up to three ``(address, room in elements)`` pairs).  -> ``(table, n_wgs)``: a ctypes array of
+    ``lib.PlanRefreshDesc`` with ``wg0`` filled in and the grid of the launch.  The library checks the contract of
+    include/dadd_hip_plan_refresh.h (sizes, alignment, every source range inside the array, room behind every
+    destination, destinations disjoint) and a breach is a ``ValueError``; nothing here needs a GPU: the addresses are
+    compared, never read."""
+    if not items:
+        raise ValueError("plan_refresh_table: no tensors")
+    table = (L.PlanRefreshDesc * len(items))()
+    for d, it in zip(table, items):
+        if it["kind"] not in PLAN_REFRESH_KINDS:
+            raise ValueError(f"plan_refresh_table: kind {it['kind']!r} is none of {sorted(PLAN_REFRESH_KINDS)}")
+        d.kind, d.N, d.K, d.Cs = PLAN_REFRESH_KINDS[it["kind"]], int(it["N"]), int(it.get("K", 0)), int(it.get("Cs", 0))
+        d.flags = int(it.get("flags", 0))
+        src, dst = list(it["src"]), list(it["dst"])
+        for i in range(4):
+            d.src_off[i] = int(src[i]) if i < len(src) else -1
+        for i in range(3):
+            d.dst[i], d.dst_room[i] = (int(dst[i][0]), int(dst[i][1])) if i < len(dst) else (None, 0)
+    lib = L.load()
+    n_wgs = lib.dadd_plan_refresh_plan(table, len(items), int(src_numel))
+    if n_wgs < 0:
+        raise ValueError((lib.dadd_last_error() or b"").decode())
+    return table, int(n_wgs)
+
+
+class PlanRefresh:
+    """Owner of the launch that writes the packed weights of live plans again from an arena's fp32 masters: the
+    device-resident descriptor tables of csrc/plan_refresh.hip, built from the ``engine.Recipe`` lists of the plans
+    (``UNetPlan.recipes``) and of the conditioning modules (``conditioning._Params.recipes``).
+
+    Every source key of a recipe must be in the arena, in the library layout.  Recipes that name the same destination
+    (plans over one weight cache) are written once.  The tables are built and uploaded once; ``refresh(source)`` is one
+    launch per 16-bit type among the destinations on the backend's stream (fp16 plans: one; bf16 plans: two, their time
+    path is fp16), ordered like ``FusedAdamW.step``.  The destinations keep their addresses: a captured graph that
+    reads them reads the new weights.  ``be=None`` gives an owner that holds the tables but cannot launch."""
+
+    def __init__(self, be, arena: ParamArena, recipes: Sequence):
+        if be is not None and arena.device != be.device:
+            raise ValueError(f"the arena lives on {arena.device}, the backend on {be.device}")
+        self.be, self.arena = be, arena
+        self.items: Dict[torch.dtype, List[dict]] = {}
+        self._dst: List[torch.Tensor] = []          # the destinations stay alive as long as their addresses are in a table
+        # Recipes count as the same when their FIRST destination starts at the same address (plans over one weight
+        # cache record identical recipes).  The library checks that destinations are disjoint within one table only;
+        # across the two tables nothing checks it: it holds because a table takes destinations of one 16-bit type and
+        # all fp32 destinations go to a single table, and a tensor has one type.
+        seen, expanded = set(), []
+        for r in recipes:
+            ptr = r.dst[0].data_ptr()
+            if ptr in seen:
+                continue
+            seen.add(ptr)
+            self._dst += list(r.dst)
+            expanded += self._expand(r)
+        if not expanded:
+            raise ValueError("PlanRefresh: no recipes")
+        # one table (= one launch) per 16-bit type among the destinations; the fp32 kinds ride with the larger one
+        count = {dt: sum(1 for it in expanded if it["kind"] not in _PR_F32 and it["out"][0][0].dtype == dt)
+                 for dt in (torch.float16, torch.bfloat16)}
+        major = torch.bfloat16 if count[torch.bfloat16] > count[torch.float16] else torch.float16
+        for it in expanded:
+            self.items.setdefault(major if it["kind"] in _PR_F32 else it["out"][0][0].dtype, []).append(it)
+        self.tables: Dict[torch.dtype, Tuple[torch.Tensor, int, int]] = {}
+        self.bytes_read = self.bytes_written = 0
+        for dtype, items in self.items.items():
+            for it in items:
+                it["dst"] = [(t.data_ptr() + off * t.element_size(), t.numel() - off) for t, off in it["out"]]
+                self.bytes_read += 4 * sum(it["reads"])
+                self.bytes_written += sum(n * t.element_size() for (t, _), n in zip(it["out"], it["writes"]))
+            host, n_wgs = plan_refresh_table(items, arena.numel)
+            words = torch.frombuffer(bytearray(bytes(host)), dtype=torch.int32)
+            table = torch.zeros(words.numel(), dtype=torch.int32, device=arena.device)
+            if be is not None:
+                be.wait_current()
+                be.copy_(table, words)
+                be.release_to_current()
+            else:
+                table.copy_(words)
+            self.tables[dtype] = (table, len(items), n_wgs)
+        self.n_launches = len(self.tables)
+
+    # -- recipes -> descriptors
+    def _src(self, s) -> Tuple[int, int, int]:
+        """(offset, rows, row length) of a source: a key or a row slice ``(key, lo, hi)``."""
+        key, lo, hi = (s, None, None) if isinstance(s, str) else s
+        if key not in self.arena.offsets:
+            raise KeyError(f"{key}: a recipe reads it, the arena does not hold it")
+        shape = tuple(self.arena.shapes[key])
+        rows = shape[0] if shape else 1
+        rowlen = (self.arena.shapes[key].numel() // rows) if rows else 0
+        lo, hi = (0 if lo is None else int(lo)), (rows if hi is None else int(hi))
+        if not 0 <= lo < hi <= rows:
+            raise ValueError(f"{key}: rows [{lo}, {hi}) of {rows}")
+        return self.arena.offsets[key] + lo * rowlen, hi - lo, rowlen
+
+    def _expand(self, r) -> List[dict]:
+        def item(kind, n, k, srcs, out, reads, writes, cs=0, flags=0):
+            return dict(kind=kind, N=n, K=k, Cs=cs, flags=flags, src=srcs, out=out, reads=reads, writes=writes)
+        out: List[dict] = []
+        if r.kind in ("copy32", "cast"):
+            off = 0
+            for s in r.src:
+                so, n, k = self._src(s)
+                if r.kind == "copy32":
+                    out.append(item("COPY32", n * k, 0, [so], [(r.dst[0], off)], [n * k], [n * k]))
+                else:
+                    out.append(item("CAST", n, k, [so], [(r.dst[0], off)], [n * k], [n * k], cs=k))
+                off += n * k
+            if off != r.dst[0].numel():
+                raise ValueError(f"{r.kind} of {r.src}: {off} source elements for a destination of {r.dst[0].numel()}")
+        elif r.kind == "cast_cin8":
+            so, n, k = self._src(r.src[0])
+            out.append(item("CAST", n * 9, 8, [so], [(r.dst[0], 0)], [n * k], [n * 72], cs=k // 9))
+        elif r.kind == "geglu":
+            so, n, k = self._src(r.src[0])
+            bo, nb, _ = self._src(r.src[1])
+            out.append(item("GEGLU_W", n, k, [so], [(r.dst[0], 0)], [n * k], [n * k]))
+            out.append(item("GEGLU_B", nb, 0, [bo], [(r.dst[1], 0)], [nb], [nb]))
+        elif r.kind == "lnfold":
+            ws, bs, gamma, beta = r.src
+            go, bo = self._src(gamma)[0], self._src(beta)[0]
+            if r.geglu and len(ws) != 1:
+                raise ValueError("lnfold in GEGLU order takes one weight")
+            row = 0
+            for i, s in enumerate(ws):
+                so, n, k = self._src(s)
+                b = self._src(bs[i])[0] if bs else -1
+                out.append(item("LNFOLD", n, k, [so, go, bo, b], [(r.dst[0], row * k), (r.dst[1], row), (r.dst[2], row)],
+                                [n * k + 2 * k + (n if bs else 0)], [n * k, n, n],
+                                flags=L.PLAN_REFRESH_GEGLU if r.geglu else 0))
+                row += n
+            if row != r.dst[1].numel():
+                raise ValueError(f"lnfold of {ws}: {row} source rows for a destination of {r.dst[1].numel()}")
+        elif r.kind == "upsfold":
+            so, n, k = self._src(r.src[0])
+            out.append(item("UPSFOLD", n, k // 9, [so], [(r.dst[0], 0)], [n * k], [16 * n * (k // 9)]))
+        elif r.kind == "head_stream":
+            srcs = [self._src(s) for s in r.src]
+            if any((n, k) != (320, 320) for _, n, k in srcs):
+                raise ValueError(f"head_stream of {r.src}: every source must be [320][320]")
+            out.append(item("HEAD_STREAM", 320, 320, [s[0] for s in srcs], [(r.dst[0], 0)], [4 * 320 * 320], [r.dst[0].numel()]))
+        elif r.kind == "ffn_stream":
+            (w1, n1, k1), (b1, nb, _), (w2, n2, k2), (wp, n3, k3) = [self._src(s) for s in r.src]
+            if (n1, k1, nb, n2, k2, n3, k3) != (2560, 320, 2560, 320, 1280, 320, 320):
+                raise ValueError(f"ffn_stream of {r.src}: the sources must be [2560][320], [2560], [320][1280], [320][320]")
+            out.append(item("FFN_STREAM", 2560, 320, [w1, w2, wp], [(r.dst[0], 0)], [2560 * 320 + 320 * 1280 + 320 * 320],
+                            [r.dst[0].numel()]))
+            out.append(item("FFN_BIAS", 2560, 320, [b1], [(r.dst[1], 0)], [2560], [2560]))
+        else:
+            raise ValueError(f"recipe kind {r.kind!r}")
+        return out
+
+    # -- the launch
+    def source(self, which: str) -> torch.Tensor:
+        if which == "raw":
+            return self.arena.p
+        if which == "ema":
+            if self.arena.ema is None:
+                raise RuntimeError("the arena has no EMA (ema=True / ensure_ema)")
+            return self.arena.ema
+        raise ValueError(f"source must be 'ema' or 'raw', got {which!r}")
+
+    def launch(self, source: str = "ema") -> None:
+        """The launches on the backend's stream, nothing else: what a graph capture records."""
+        if self.be is None:
+            raise RuntimeError("PlanRefresh was built without a backend: it holds the tables but cannot launch")
+        src = self.source(source)
+        for dtype, (table, n_desc, n_wgs) in self.tables.items():
+            self.be.plan_refresh(src, table, n_desc, n_wgs, dtype)
+
+    def refresh(self, source: str = "ema") -> None:
+        """Write every destination again from the arena's EMA (``"ema"``) or its raw masters (``"raw"``).  Ordered after
+        torch's current stream and before what it does next, like ``FusedAdamW.step``; no host sync."""
+        if self.be is None:
+            raise RuntimeError("PlanRefresh was built without a backend: it holds the tables but cannot launch")
+        capturing = self.be._capturing
+        if not capturing:
+            self.be.wait_current()
+        self.launch(source)
+        if not capturing:
+            self.be.release_to_current()
 
 
 def reference_param_groups(names: Sequence[str], lr: float, weight_decay: float = 0.0) -> List[dict]:

@@ -5,7 +5,9 @@ around a ``DiffusionModuleWithIP``.
 
 The module stays what it is: its frozen parts (VAE encoder, CLIP tower, noise schedule) serve the trainer as they serve
 ``training_step()``, and ``training_step()`` / ``configure_optimizers()`` keep their behaviour.  The trainer owns its own
-fp32 masters, taken from the module's state dict once; the module's inference plans do not follow them.
+fp32 masters, taken from the module's state dict once.  ``sync_module("ema" | "raw")`` hands them to the module's live
+inference plans and conditioning modules in place, by one refresh launch (``optim.PlanRefresh``, csrc/plan_refresh.hip):
+weight buffers keep their addresses, so captured ``DdimLoop`` graphs sample with the new weights.
 ``export_state_dict()`` gives the trained weights back in the reference layout, which ``DiffusionModuleWithIP(cfg,
 state_dict=...)`` loads.
 
@@ -112,6 +114,7 @@ class Trainer:
         self._found_inf = self.optimizer.state[L.OptimState.found_inf.offset // 4:L.OptimState.found_inf.offset // 4 + 1]
         self._last_drop = None
         self._writer = IO.BackgroundWriter()
+        self._refresher = None              # sync_module: (owners, recipes per owner, PlanRefresh) of the last call
         self._copy_stream = None
         self._lrs = None
         self.set_epoch(0)
@@ -274,6 +277,53 @@ class Trainer:
                 masters[k] = view(k).detach().cpu()
         return UG.state_dict_from_masters(masters)
 
+    # -- trained weights -> the module's live plans
+    def _plan_refresh(self, owners) -> "O.PlanRefresh":
+        bad = [(type(o).__name__, o.unrefreshable[:3]) for o in owners if o.unrefreshable]
+        if bad:
+            raise RuntimeError(f"sync_module: weight uploads without a recipe, they cannot be refreshed in place: {bad}")
+        return O.PlanRefresh(self.be, self.arena, [r for o in owners for r in o.recipes])
+
+    def _sync_plan(self, plan) -> None:
+        """``module._plan_sync``: a plan built after a ``sync_module`` takes the weights the source synced last holds NOW,
+        not those of the moment of that sync: if optimizer steps ran in between, the new plan is ahead of the older live
+        plans until the next ``sync_module`` brings all to one state.  Its table is built, used once and dropped (plans
+        are built rarely; the kept table of ``sync_module`` covers the set that was live then).  The hook belongs to the
+        trainer whose ``sync_module`` ran last on the module."""
+        self._plan_refresh([plan]).refresh(self.module._synced)
+        plan.weights_gen += 1
+
+    def sync_module(self, which: str = "ema") -> None:
+        """Hand the trained weights - their EMA (``"ema"``) or the raw masters (``"raw"``) - to the module's live inference
+        plans (every ``UNetPlan`` in ``module._unets``) and its conditioning modules (ordinal embedder, image projection,
+        feature purifier), in place: one refresh launch per 16-bit type (``optim.PlanRefresh``), no host copy, no
+        synchronisation.  Weight buffers keep their addresses, so an already captured ``DdimLoop`` graph stays valid and
+        samples with the new weights.  Each plan gets ``_a2_dirty`` and an advanced ``cond_gen`` / ``weights_gen``: the
+        projected K/V, the attn2 fold and a ``DdimLoop``'s time-row table are rebuilt at the next ``set_cond`` /
+        ``prepare_attn2`` / ``prepare``.  The module remembers the source: a plan it
+        builds later is refreshed before it is handed out.  ``module._sd`` is not rewritten (``export_state_dict()``
+        stays the way to a state dict); VAE, CLIP tower and routing gates are not trained and not touched.  Raises
+        ``RuntimeError`` while micro-batches are pending, like ``state()``."""
+        if which not in ("ema", "raw"):
+            raise ValueError(f"sync_module: which must be 'ema' or 'raw', got {which!r}")
+        if self.pending:
+            raise RuntimeError(f"{self.pending} micro-batch(es) are pending: flush() or optimizer_step() before the weights "
+                               "are handed to the module")
+        mod = self.module
+        plans = [u._plan for u in mod._unets.values()]
+        conds = [m for m in (mod.ordinal_embedder, mod.image_projection, mod.feature_purifier) if m is not None]
+        owners, counts = plans + conds, [len(o.recipes) for o in plans + conds]
+        last = self._refresher
+        # the tables are kept while the same plans and modules are live and none has packed a new tensor since
+        if last is None or len(last[0]) != len(owners) or any(a is not b for a, b in zip(last[0], owners)) or last[1] != counts:
+            last = self._refresher = (owners, counts, self._plan_refresh(owners))
+        last[2].refresh(which)
+        for plan in plans:
+            plan._a2_dirty = True
+            plan.cond_gen += 1
+            plan.weights_gen += 1           # DdimLoop rebuilds its time-row table
+        mod._synced, mod._plan_sync = which, self._sync_plan
+
     # -- state and checkpoints
     def _untrained(self) -> List[str]:
         return [k for k in self.module._sd if k.startswith(_FROZEN) or k in self.gates]
@@ -387,7 +437,8 @@ class Trainer:
 
     # -- the run
     def fit(self, batches, *, epochs: Optional[int] = None, on_log: Optional[Callable[[dict], None]] = None,
-            log_every: Optional[int] = None, ckpt_dir=None, resume=None) -> List[dict]:
+            log_every: Optional[int] = None, ckpt_dir=None, resume=None,
+            preview: Optional[Callable[["Trainer", int], None]] = None, preview_every: int = 1) -> List[dict]:
         """Train over ``batches`` - any re-iterable of ``(images, labels, clip_pixel_values)``, iterated once per epoch -
         up to epoch ``epochs`` (exclusive; default ``cfg.training.max_epochs``).  Per epoch: ``set_epoch``, ``step()``
         per batch, ``flush()``, and with ``ckpt_dir`` a background ``save_checkpoint(ckpt_dir/last.ckpt)``.  After every
@@ -395,6 +446,8 @@ class Trainer:
         handed to ``on_log`` and kept; that is the loop's only synchronisation.  ``resume``: ``None``, ``"last"`` or a
         path (``training_io.resolve_resume``); training continues at the epoch after the saved one (the position inside
         an epoch is not kept: checkpoints are written at epoch ends).  A second call continues where the first stopped.
+        ``preview``: after every ``preview_every``-th epoch (after its flush) ``sync_module("ema")`` and then
+        ``preview(trainer, epoch)`` - the module samples with the averaged weights there; ``None`` leaves the loop as it is.
         -> the logged dicts."""
         path = IO.resolve_resume(resume, ckpt_dir)
         if path is not None:
@@ -419,6 +472,9 @@ class Trainer:
                 if self.flush():
                     log()
                 self.next_epoch = e + 1
+                if preview is not None and (e + 1) % max(1, int(preview_every)) == 0:
+                    self.sync_module("ema")
+                    preview(self, e)
                 if ckpt_dir is not None:
                     self.save_checkpoint(os.path.join(str(ckpt_dir), IO.LAST), wait=False)
         finally:
