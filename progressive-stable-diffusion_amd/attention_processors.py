@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
+from .backend import on_backend
 from .routing import get_block_type, get_frequency_mode_for_block  # noqa: F401  (reference names)
 
 F16 = torch.float16
@@ -65,27 +66,26 @@ class _HipCrossAttention(nn.Module):
         b, n, c = hidden_states.shape
         t = encoder_hidden_states.shape[1]
         heads = attn.heads
-        be.wait_current()
-        x16 = be.to_device(hidden_states.detach().reshape(b, 1, n, c), F16)
-        # step-invariant: K/V projections of the conditioning tokens, cached per tensor
-        # (the cache holds the tensor itself, so its storage cannot be recycled under the same address)
-        key = encoder_hidden_states._version
-        if getattr(self, "_kv_src", None) is not encoder_hidden_states or self._kv_key != key:
-            w_kv = be.to_device(self._kv_weight(attn).detach(), F16)
-            cond16 = be.to_device(encoder_hidden_states.detach().reshape(b, 1, t, -1), F16)
-            kv = be.empty((b, 1, t, w_kv.shape[0]), F16)
-            be.igemm(cond16, w_kv, kv, flags=L.TUNE_NODMA, tile_m=64)
-            self._kv, self._kv_key, self._kv_src = kv, key, encoder_hidden_states
-        q = be.empty((b, 1, n, c), F16)
-        be.igemm(x16, self._w16(be, "q", attn.to_q.weight), q, flags=L.TUNE_NODMA, tile_m=64)
-        att = be.empty((b, n, c), F16)
-        be.tri_xattn(q.view(b, n, c), self._kv.view(b, t, -1), att, gates, lam, self.mode, heads)
-        out = be.empty((b, 1, n, c), F16)
-        to_out = attn.to_out[0]
-        bias = None if getattr(to_out, "bias", None) is None else self._w16(be, "ob", to_out.bias, torch.float32)
-        be.igemm(att.view(b, 1, n, c), self._w16(be, "o", to_out.weight), out, bias=bias,
-                 flags=(L.EPI_BIAS if bias is not None else 0) | L.TUNE_NODMA, tile_m=64)
-        be.release_to_current()
+        with on_backend(be):
+            x16 = be.to_device(hidden_states.detach().reshape(b, 1, n, c), F16)
+            # step-invariant: K/V projections of the conditioning tokens, cached per tensor
+            # (the cache holds the tensor itself, so its storage cannot be recycled under the same address)
+            key = encoder_hidden_states._version
+            if getattr(self, "_kv_src", None) is not encoder_hidden_states or self._kv_key != key:
+                w_kv = be.to_device(self._kv_weight(attn).detach(), F16)
+                cond16 = be.to_device(encoder_hidden_states.detach().reshape(b, 1, t, -1), F16)
+                kv = be.empty((b, 1, t, w_kv.shape[0]), F16)
+                be.igemm(cond16, w_kv, kv, flags=L.TUNE_NODMA, tile_m=64)
+                self._kv, self._kv_key, self._kv_src = kv, key, encoder_hidden_states
+            q = be.empty((b, 1, n, c), F16)
+            be.igemm(x16, self._w16(be, "q", attn.to_q.weight), q, flags=L.TUNE_NODMA, tile_m=64)
+            att = be.empty((b, n, c), F16)
+            be.tri_xattn(q.view(b, n, c), self._kv.view(b, t, -1), att, gates, lam, self.mode, heads)
+            out = be.empty((b, 1, n, c), F16)
+            to_out = attn.to_out[0]
+            bias = None if getattr(to_out, "bias", None) is None else self._w16(be, "ob", to_out.bias, torch.float32)
+            be.igemm(att.view(b, 1, n, c), self._w16(be, "o", to_out.weight), out, bias=bias,
+                     flags=(L.EPI_BIAS if bias is not None else 0) | L.TUNE_NODMA, tile_m=64)
         hidden_states = attn.to_out[1](out.view(b, n, c).to(residual.dtype))
         if input_ndim == 4:
             hidden_states = hidden_states.transpose(-1, -2).reshape(b, c, h, w)

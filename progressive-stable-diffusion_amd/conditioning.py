@@ -22,6 +22,7 @@ from typing import Dict, Iterator, Optional
 import torch
 
 from . import lib as L
+from .backend import on_backend
 from .engine import Recipe, fold_layernorm, plan_tiling
 
 F16, F32 = torch.float16, torch.float32
@@ -152,11 +153,8 @@ class _Params:
 def _io(fn):
     """Class-boundary stream discipline: inputs produced on torch's current stream, outputs consumed there."""
     def wrapped(self, *a, **k):
-        self.be.wait_current()
-        try:
+        with on_backend(self.be):
             return fn(self, *a, **k)
-        finally:
-            self.be.release_to_current()
     wrapped.__doc__ = fn.__doc__
     return wrapped
 

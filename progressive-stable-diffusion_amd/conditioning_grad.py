@@ -25,6 +25,7 @@ from __future__ import annotations
 import torch
 
 from . import grad_ops as G
+from .backend import on_backend
 
 
 def _lin(be, params, key, x):
@@ -117,7 +118,7 @@ def time_embedding(be, params, t, proj_keys, dim=320, prefix="unet.unet.time_emb
     gradient of the concatenation)."""
     f16 = torch.float16
     t = t.reshape(-1).to(torch.int64).contiguous()
-    with G.on_backend(be):
+    with on_backend(be):
         feat = be.empty((t.shape[0], dim), torch.float32)
         be.timestep_features(t, feat)
     h = G.linear_rows(be, feat, params[prefix + ".linear_1.weight"], params[prefix + ".linear_1.bias"], weight_dtype=f16)

@@ -23,6 +23,7 @@ from typing import Any, Dict, Iterator, Optional, Tuple
 import torch
 
 from . import weights as W
+from .backend import on_backend
 from .conditioning import (AdditiveOrdinalEmbedder, FeaturePurifier, ImageEncoder, ImageProjection,
                            ImageProjectionPlus)
 from .engine import DdimLoop, UNetPlan, VaeDecoderPlan
@@ -107,6 +108,7 @@ class _InnerUNet:
 
     def __init__(self, plan: UNetPlan, routing: bool):
         self._plan = plan
+        self._cond_ref, self._cond_ver, self._cond_gen = None, -1, -1
         self.config = SimpleNamespace(in_channels=4, out_channels=4, cross_attention_dim=768,
                                       block_out_channels=[320, 640, 1280, 1280], sample_size=64)
         self._sites = {}
@@ -127,11 +129,42 @@ class _InnerUNet:
             raise ValueError(f"attention processors disagree on delta_scale: {sorted(vals)}")
         return vals.pop()
 
+    def eps(self, latents, timesteps, cond_embed):
+        """The one way into the plan, for ``OrdinalUNet.__call__`` and for ``__call__`` below: argument normalisation, the
+        conditioning cache, the stream bracket, ``plan.forward``.  ``timesteps``: a tensor of any shape or a Python
+        scalar; ``cond_embed=None`` reuses the projections of the previous call.  -> eps, fp32 NCHW."""
+        cond_in = cond_embed                  # identity of the caller's tensor (views below are new objects)
+        if cond_embed is not None:
+            if cond_embed.ndim == 2:
+                cond_embed = cond_embed.unsqueeze(1)
+            elif cond_embed.ndim != 3:
+                raise ValueError(f"cond_embed must have shape (B, D) or (B, seq_len, D), got {cond_embed.shape}")
+        plan = self._plan
+        be = plan.be
+        # dtype / device / shape normalisation runs on torch's CURRENT stream, i.e. before the bracket's wait_current()
+        # orders the backend stream behind it (a scalar, CPU or non-fp32 input is produced here)
+        timesteps = torch.as_tensor(timesteps).to(device=latents.device, dtype=torch.long).reshape(-1)
+        if timesteps.shape[0] == 1:
+            timesteps = timesteps.expand(plan.B)
+        timesteps = timesteps.contiguous()
+        latents = latents.float().contiguous()
+        # Conditioning tensors are step-invariant: re-project only when the caller passes a new one.  The cache
+        # HOLDS the tensor (an address can be recycled by the allocator) and is tied to the plan's conditioning
+        # generation, which every set_cond() — e.g. a sampler run on the same plan — advances.
+        fresh = cond_in is not None and not (cond_in is self._cond_ref and cond_in._version == self._cond_ver
+                                             and plan.cond_gen == self._cond_gen)
+        if fresh:
+            cond_embed = cond_embed.to(device=latents.device)
+        with on_backend(be):
+            eps = plan.forward(latents, timesteps, cond_embed if fresh else None, lam=self.delta_scale())
+            if fresh:
+                self._cond_ref, self._cond_ver, self._cond_gen = cond_in, cond_in._version, plan.cond_gen
+        return eps
+
     def __call__(self, sample, timestep, encoder_hidden_states=None, **_):
         """``UNet2DConditionModel.forward`` as OrdinalUNet.forward uses it (src/models/unet/unet.py:140-144):
         ``unet(sample, timestep, encoder_hidden_states=cond).sample``."""
-        eps = self._plan.forward(sample.float(), timestep, encoder_hidden_states, lam=self.delta_scale())
-        return SimpleNamespace(sample=eps)
+        return SimpleNamespace(sample=self.eps(sample, timestep, encoder_hidden_states))
 
 
 class OrdinalUNet:
@@ -149,7 +182,6 @@ class OrdinalUNet:
             raise ValueError(f"UNet cross_attention_dim mismatch: {c.cross_attention_dim} (from weights) "
                              f"vs {conditioning_dim} (config).")
         self._plan = plan
-        self._cond_ref, self._cond_ver, self._cond_gen = None, -1, -1
 
     # ``module.unet.unet = torch.compile(module.unet.unet, mode="reduce-overhead")`` (the reference's --compile switch,
     # src/pipelines/inference/inference_pipeline_ip_data_augment.py:398-400): the assignment is accepted and the wrapper kept
@@ -170,37 +202,7 @@ class OrdinalUNet:
         return iter(self._plan.keep)
 
     def __call__(self, latents, timesteps, cond_embed):
-        cond_in = cond_embed                  # identity of the caller's tensor (views below are new objects)
-        if cond_embed.ndim == 2:
-            cond_embed = cond_embed.unsqueeze(1)
-        elif cond_embed.ndim != 3:
-            raise ValueError(f"cond_embed must have shape (B, D) or (B, seq_len, D), got {cond_embed.shape}")
-        if timesteps.ndim == 0:
-            timesteps = timesteps[None]
-        elif timesteps.ndim > 1:
-            timesteps = timesteps.view(-1)
-        plan = self._plan
-        be = plan.be
-        # dtype / device / shape normalisation runs on torch's CURRENT stream, i.e. before wait_current()
-        # orders the backend stream behind it (a scalar, CPU or non-fp32 input is produced here)
-        timesteps = timesteps.to(device=latents.device, dtype=torch.long).reshape(-1)
-        if timesteps.shape[0] == 1:
-            timesteps = timesteps.expand(plan.B)
-        timesteps = timesteps.contiguous()
-        latents = latents.float().contiguous()
-        # Conditioning tensors are step-invariant: re-project only when the caller passes a new one.  The cache
-        # HOLDS the tensor (an address can be recycled by the allocator) and is tied to the plan's conditioning
-        # generation, which every set_cond() — e.g. a sampler run on the same plan — advances.
-        fresh = not (cond_in is self._cond_ref and cond_in._version == self._cond_ver
-                     and plan.cond_gen == self._cond_gen)
-        if fresh:
-            cond_embed = cond_embed.to(device=latents.device)
-        be.wait_current()
-        eps = plan.forward(latents, timesteps, cond_embed if fresh else None, lam=self.unet.delta_scale())
-        if fresh:
-            self._cond_ref, self._cond_ver, self._cond_gen = cond_in, cond_in._version, plan.cond_gen
-        be.release_to_current()
-        return eps
+        return self.unet.eps(latents, timesteps, cond_embed)
 
     forward = __call__
 
@@ -233,11 +235,10 @@ class SDVAE:
             raise ValueError(f"latents must be (B, 4, S, S), got {tuple(latents.shape)}")
         plan = self._plan(b, h)
         be = self._be
-        be.wait_current()
-        be.copy_(plan.z_in, latents.float())
-        plan.run()
-        img = be.clone(plan.img_out)           # [0,1] frames; see sample_is_unit_range
-        be.release_to_current()
+        with on_backend(be):
+            be.copy_(plan.z_in, latents.float())
+            plan.run()
+            img = be.clone(plan.img_out)       # [0,1] frames; see sample_is_unit_range
         # The reference decoder returns [-1,1] and _latents_to_images maps to [0,1]; the HIP decoder
         # fuses that tail into its last kernel, so hand back the equivalent [-1,1] tensor here.
         out = img * 2.0 - 1.0
@@ -263,11 +264,10 @@ class SDVAE:
         plan = self._enc_plan(b, h // 8)
         be = self._be
         x = images.float().contiguous()
-        be.wait_current()
-        be.copy_(plan.img_in, x)
-        plan.run()
-        dist = DiagonalGaussian(be, be.clone(plan.mean), be.clone(plan.logvar))
-        be.release_to_current()
+        with on_backend(be):
+            be.copy_(plan.img_in, x)
+            plan.run()
+            dist = DiagonalGaussian(be, be.clone(plan.mean), be.clone(plan.logvar))
         return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
 
 
@@ -297,10 +297,9 @@ class DiagonalGaussian:
             noise = torch.randn(self.mean.shape, generator=generator, device=self.mean.device, dtype=torch.float32)
         else:
             noise = noise.to(device=self.mean.device, dtype=torch.float32).contiguous()
-        be.wait_current()
-        out = be.empty(self.mean.shape, torch.float32)
-        be.gaussian_sample(self.mean, self.logvar, noise, out, scale)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty(self.mean.shape, torch.float32)
+            be.gaussian_sample(self.mean, self.logvar, noise, out, scale)
         return out
 
 
@@ -482,10 +481,9 @@ class DiffusionModuleWithIP:
         x0 = x0.to(device=self.device, dtype=torch.float32).contiguous()
         noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
         t = t.to(device=self.device, dtype=torch.long).contiguous()
-        be.wait_current()
-        out = be.empty(tuple(x0.shape), torch.float32)
-        be.q_sample(x0, noise, t, self.alphas_cumprod, out)
-        be.release_to_current()
+        with on_backend(be):
+            out = be.empty(tuple(x0.shape), torch.float32)
+            be.q_sample(x0, noise, t, self.alphas_cumprod, out)
         return out
 
     def _min_snr_weight(self, t: torch.Tensor) -> torch.Tensor:
@@ -536,10 +534,9 @@ class DiffusionModuleWithIP:
         cond = torch.cat([aoe, img, parts[2]] if self.diff_cfg.use_routing_gates else [aoe, img], dim=1)
         pred = self(noisy, t, cond)
         be = self.be
-        be.wait_current()
-        base = be.empty((b,), torch.float32)
-        be.mse_rows(pred.contiguous(), noise.contiguous(), base)
-        be.release_to_current()
+        with on_backend(be):
+            base = be.empty((b,), torch.float32)
+            be.mse_rows(pred.contiguous(), noise.contiguous(), base)
         return (self._min_snr_weight(t) * base).mean()
 
     def configure_optimizers(self):

@@ -14,6 +14,8 @@ from typing import List, Tuple
 import torch
 import torch.distributed as dist
 
+from .backend import on_backend
+
 
 def init_from_env(backend: str | None = None) -> Tuple[int, int, int]:
     """(rank, world, local_rank) from torchrun's environment; a no-op for a single process."""
@@ -80,10 +82,9 @@ def all_gather_frames_u8(be, frames: torch.Tensor, n_total: int | None = None) -
     GPU first (``dadd_frames_to_u8``: what the writers consume; 3.1 MB instead of 12.6 MB per rank at 512x512, b = 4),
     then ONE all-gather -> (world*b, H, W, 3) uint8 on every rank, rank-major."""
     b, _, h, w = frames.shape
-    be.wait_current()
-    u8 = be.zeros((b, h, w, 3), torch.uint8)
-    be.frames_to_u8(frames.float().contiguous(), u8)
-    be.release_to_current()
+    with on_backend(be):
+        u8 = be.zeros((b, h, w, 3), torch.uint8)
+        be.frames_to_u8(frames.float().contiguous(), u8)
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         out = u8
     else:

@@ -26,6 +26,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import lib as L
+from .backend import on_backend
 from .routing import get_block_type  # noqa: F401  (re-exported for callers)
 
 F16, F32, BF16 = torch.float16, torch.float32, torch.bfloat16
@@ -1355,15 +1356,13 @@ class DdimLoop:
         """All prepared steps from ``latents`` -> final latents, WITH both stream hand-offs: the backend stream waits
         for whatever torch's current stream has queued (conditioning caches written by torch ops, the latents), and
         the current stream waits for the returned tensor.  Callers that drive ``prepare`` / ``run`` by hand owe the
-        same two calls (``be.wait_current()`` before, ``be.release_to_current()`` after)."""
+        same bracket (``with on_backend(be):``)."""
         be = self.be
-        be.wait_current()
-        self.prepare(timesteps, alphas_cumprod)
-        be.copy_(self.u.lat_in, latents)
-        self.run(lam, do_cfg, guidance, use_graph=use_graph, trace=trace)
-        out = be.clone(self.u.lat_in)
-        be.release_to_current()
-        return out
+        with on_backend(be):
+            self.prepare(timesteps, alphas_cumprod)
+            be.copy_(self.u.lat_in, latents)
+            self.run(lam, do_cfg, guidance, use_graph=use_graph, trace=trace)
+            return be.clone(self.u.lat_in)
 
     def _one_step(self, lam: float, do_cfg: bool, guidance: float, keep_eps: bool = False):
         """``keep_eps``: eps of the step stays readable in ``unet.eps_out`` (traces); otherwise, without CFG, conv_out

@@ -147,7 +147,7 @@ class FrameSink:
         self.slot = (self.slot + 1) % len(self.host)
         self._drain(i)                                  # the slot's previous files are on disk
         be = self.be
-        be.wait_current()
+        be.wait_current()                               # half a hand-off: the event below hands on to the copy stream
         be.frames_to_u8(frames.float().contiguous(), self.dev_u8[i][:b])
         if self.copy_stream is not None:
             ev = torch.cuda.Event()

@@ -45,25 +45,7 @@ from __future__ import annotations
 import torch
 
 from . import lib as L
-
-
-class on_backend:
-    """The stream bracket of every operator here, ``with on_backend(be):`` - inside it the backend's stream runs after what
-    torch's current stream has produced, and after it (also when the body raises) torch's current stream waits for the
-    backend's.  Everything that allocates or launches through ``be`` goes inside; leaving either end out is a cross-stream
-    race that no test would catch.  Uses ``be.wait_current()`` and ``be.release_to_current()`` alone, so any backend with
-    those two serves.  A plain class, not a ``contextlib`` generator: a step enters it a few thousand times, and this form
-    costs 0.2 us more than the two bare calls where the generator costs 1 us."""
-    __slots__ = ("be",)
-
-    def __init__(self, be):
-        self.be = be
-
-    def __enter__(self):
-        self.be.wait_current()
-
-    def __exit__(self, *exc):
-        self.be.release_to_current()
+from .backend import on_backend      # the stream bracket; ``grad_ops.on_backend`` stays importable
 
 
 def dgrad_weight(w16: torch.Tensor, taps: int) -> torch.Tensor:

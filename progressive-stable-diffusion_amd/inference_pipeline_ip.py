@@ -197,7 +197,7 @@ def _ddim_sample_ip(module: DiffusionModuleWithIP, target_labels: Tensor, source
 
     loop = module.ddim_loop(num_samples, side)
     plan, be = loop.u, loop.be
-    be.wait_current()
+    be.wait_current()                   # half a hand-off: loop.sample() below releases
     plan.set_cond(embed_cond, 0)
     if do_cfg:
         plan.set_cond(embed_uncond, 1)

@@ -27,6 +27,7 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import torch
 
 from . import lib as L
+from .backend import on_backend
 
 CHUNK = L.OPTIM_CHUNK
 _ALIGN = 8          # elements: 32 bytes of fp32, 16 bytes of the 16-bit copy
@@ -188,7 +189,39 @@ def relayout_dst_numel(kind: str, taps: int, n: int, c: int) -> int:
     return int(r)
 
 
-class DgradRelayout:
+class _Launcher:
+    """What ``DgradRelayout``, ``PlanRefresh`` and ``FusedAdamW`` share: ``be`` (``None``: the owner holds its device
+    blocks but cannot launch), the upload of a ctypes block, and the stream bracket around ``launch()``."""
+    _HOLDS = ""         # how the "built without a backend" error ends, in the owner's words
+
+    def _need_backend(self) -> None:
+        if self.be is None:
+            raise RuntimeError(f"{type(self).__name__} was built without a backend: {self._HOLDS}")
+
+    def _upload_words(self, block, dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A ctypes block as int32 words into ``dst`` (default: a new tensor on the arena's device), through the backend's
+        stream when there is one."""
+        words = torch.frombuffer(bytearray(bytes(block)), dtype=torch.int32)
+        if dst is None:
+            dst = torch.zeros(words.numel(), dtype=torch.int32, device=self.arena.device)
+        if self.be is not None:
+            # half a hand-off: ``dst`` (and the moments a load wrote) were produced on torch's stream; only the backend's
+            # stream reads the block, and the bracket of the next refresh() / step() releases
+            self.be.wait_current()
+            self.be.copy_(dst, words)
+        else:
+            dst.copy_(words)
+        return dst
+
+    def _bracketed_launch(self, *args) -> None:
+        """``launch(*args)`` ordered after torch's current stream and before what it does next; in a graph capture the
+        bracket does nothing and the bare launches are recorded."""
+        self._need_backend()
+        with on_backend(self.be):
+            self.launch(*args)
+
+
+class DgradRelayout(_Launcher):
     """Owner of the data-gradient layouts of an arena's weights: a flat 16-bit buffer ``wt`` beside ``arena.p16`` and the
     device-resident descriptor table of the launch that fills it.
 
@@ -197,6 +230,7 @@ class DgradRelayout:
     (``dgrad_weight_ups``), ``"COUT4"`` (``dgrad_weight_cout4``).  Buffer and table are allocated once; ``refresh()`` is
     one launch on the backend's stream, ordered like ``FusedAdamW.step``.  ``w16(name)`` / ``wt(name)`` are the views a
     ``grad_ops`` product takes as ``prepared=``.  ``be=None`` gives an owner that holds the table but cannot launch."""
+    _HOLDS = "it holds the table but cannot launch"
 
     def __init__(self, be, arena: ParamArena, entries: Sequence[tuple]):
         if arena.p16 is None:
@@ -228,32 +262,17 @@ class DgradRelayout:
         self._table, self.n_tiles = relayout_plan(items, arena.numel, self.numel)
         self.n_desc = len(items)
         self.buf = torch.zeros(self.numel, dtype=arena.p16.dtype, device=arena.device)
-        words = torch.frombuffer(bytearray(bytes(self._table)), dtype=torch.int32)
-        self.table = torch.zeros(words.numel(), dtype=torch.int32, device=arena.device)
-        if be is not None:
-            be.wait_current()
-            be.copy_(self.table, words)
-            be.release_to_current()
-        else:
-            self.table.copy_(words)
+        self.table = self._upload_words(self._table)
 
     def launch(self) -> None:
         """The one launch on the backend's stream, nothing else: what a graph capture records."""
-        if self.be is None:
-            raise RuntimeError("DgradRelayout was built without a backend: it holds the table but cannot launch")
+        self._need_backend()
         self.be.dgrad_relayout(self.arena.p16, self.buf, self.table, self.n_desc, self.n_tiles)
 
     def refresh(self) -> None:
         """Re-lay every listed weight from the arena's current ``p16``.  Ordered after torch's current stream and before
         what it does next, like ``FusedAdamW.step``; no host sync."""
-        if self.be is None:
-            raise RuntimeError("DgradRelayout was built without a backend: it holds the table but cannot launch")
-        capturing = self.be._capturing
-        if not capturing:
-            self.be.wait_current()
-        self.launch()
-        if not capturing:
-            self.be.release_to_current()
+        self._bracketed_launch()
 
     def w16(self, name: str) -> torch.Tensor:
         """The 16-bit working copy of ``name``: ``arena.param16``."""
@@ -307,7 +326,7 @@ def plan_refresh_table(items: Sequence[dict], src_numel: int):
     return table, int(n_wgs)
 
 
-class PlanRefresh:
+class PlanRefresh(_Launcher):
     """Owner of the launch that writes the packed weights of live plans again from an arena's fp32 masters: the
     device-resident descriptor tables of csrc/plan_refresh.hip, built from the ``engine.Recipe`` lists of the plans
     (``UNetPlan.recipes``) and of the conditioning modules (``conditioning._Params.recipes``).
@@ -317,6 +336,7 @@ class PlanRefresh:
     launch per 16-bit type among the destinations on the backend's stream (fp16 plans: one; bf16 plans: two, their time
     path is fp16), ordered like ``FusedAdamW.step``.  The destinations keep their addresses: a captured graph that
     reads them reads the new weights.  ``be=None`` gives an owner that holds the tables but cannot launch."""
+    _HOLDS = "it holds the tables but cannot launch"
 
     def __init__(self, be, arena: ParamArena, recipes: Sequence):
         if be is not None and arena.device != be.device:
@@ -352,15 +372,7 @@ class PlanRefresh:
                 self.bytes_read += 4 * sum(it["reads"])
                 self.bytes_written += sum(n * t.element_size() for (t, _), n in zip(it["out"], it["writes"]))
             host, n_wgs = plan_refresh_table(items, arena.numel)
-            words = torch.frombuffer(bytearray(bytes(host)), dtype=torch.int32)
-            table = torch.zeros(words.numel(), dtype=torch.int32, device=arena.device)
-            if be is not None:
-                be.wait_current()
-                be.copy_(table, words)
-                be.release_to_current()
-            else:
-                table.copy_(words)
-            self.tables[dtype] = (table, len(items), n_wgs)
+            self.tables[dtype] = (self._upload_words(host), len(items), n_wgs)
         self.n_launches = len(self.tables)
 
     # -- recipes -> descriptors
@@ -446,8 +458,7 @@ class PlanRefresh:
 
     def launch(self, source: str = "ema") -> None:
         """The launches on the backend's stream, nothing else: what a graph capture records."""
-        if self.be is None:
-            raise RuntimeError("PlanRefresh was built without a backend: it holds the tables but cannot launch")
+        self._need_backend()
         src = self.source(source)
         for dtype, (table, n_desc, n_wgs) in self.tables.items():
             self.be.plan_refresh(src, table, n_desc, n_wgs, dtype)
@@ -455,14 +466,7 @@ class PlanRefresh:
     def refresh(self, source: str = "ema") -> None:
         """Write every destination again from the arena's EMA (``"ema"``) or its raw masters (``"raw"``).  Ordered after
         torch's current stream and before what it does next, like ``FusedAdamW.step``; no host sync."""
-        if self.be is None:
-            raise RuntimeError("PlanRefresh was built without a backend: it holds the tables but cannot launch")
-        capturing = self.be._capturing
-        if not capturing:
-            self.be.wait_current()
-        self.launch(source)
-        if not capturing:
-            self.be.release_to_current()
+        self._bracketed_launch(source)
 
 
 def reference_param_groups(names: Sequence[str], lr: float, weight_decay: float = 0.0) -> List[dict]:
@@ -493,7 +497,7 @@ def arena_from_groups(tensors: Mapping[str, torch.Tensor], groups: Sequence[dict
     return ParamArena(OrderedDict((k, tensors[k]) for g in groups for k in g["params"]), group_of, **kw)
 
 
-class FusedAdamW:
+class FusedAdamW(_Launcher):
     """AdamW over a ``ParamArena`` on the kernels of csrc/optim.hip.
 
     ``groups``: one ``{"lr", "weight_decay"}`` per arena group (further keys are ignored, so the list of
@@ -504,6 +508,7 @@ class FusedAdamW:
     tensor (a device scalar, no sync).  ``ema_decay`` allocates the arena's EMA; ``working_dtype`` its 16-bit copy
     (default: what the arena already has).  ``be=None`` gives an optimizer that holds state but cannot step (CPU).
     """
+    _HOLDS = "it holds state but cannot step"
 
     def __init__(self, be, arena: ParamArena, groups: Sequence[Mapping], *, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_grad_norm: float = 0.0, ema_decay: Optional[float] = None,
@@ -531,9 +536,7 @@ class FusedAdamW:
             host.lr[k] = float(g["lr"])
             hg.beta1, hg.beta2, hg.eps, hg.weight_decay = b1, b2, float(g.get("eps", eps)), float(g["weight_decay"])
             hg.one_minus_beta1, hg.one_minus_beta2 = 1.0 - b1, 1.0 - b2
-        self._words = C.sizeof(L.OptimState) // 4
-        self.state = torch.zeros(self._words, dtype=torch.int32, device=arena.device)
-        self._upload(host)
+        self.state = self._upload_words(host)
         self.partials = torch.empty(arena.n_chunks, dtype=torch.float32, device=arena.device)
         self.flags = torch.empty(arena.n_chunks, dtype=torch.int32, device=arena.device)
         self._group_chunks = (C.c_int * arena.n_groups)(*arena.group_chunks)
@@ -542,12 +545,7 @@ class FusedAdamW:
 
     # -- the state block
     def _upload(self, host: "L.OptimState") -> None:
-        words = torch.frombuffer(bytearray(bytes(host)), dtype=torch.int32)
-        if self.be is not None:
-            self.be.wait_current()          # the block (and the moments a load wrote) were produced on torch's stream
-            self.be.copy_(self.state, words)
-        else:
-            self.state.copy_(words)
+        self._upload_words(host, self.state)
 
     def _download(self) -> "L.OptimState":
         if self.be is not None:
@@ -586,8 +584,7 @@ class FusedAdamW:
 
     def launch(self, update_ema: bool = False, zero_grad: bool = True) -> None:
         """The three launches on the backend's stream, nothing else: what a graph capture records."""
-        if self.be is None:
-            raise RuntimeError("FusedAdamW was built without a backend: it holds state but cannot step")
+        self._need_backend()
         a, be = self.arena, self.be
         flags = self._flags(update_ema, zero_grad)
         be.optim_grad_stats(a.g, self.partials, self.flags, max_blocks=self.max_blocks)
@@ -600,14 +597,7 @@ class FusedAdamW:
         """One optimizer step on the gradients in the arena: clip, unscale, AdamW, and in the same pass the 16-bit copy,
         with ``update_ema`` the EMA and with ``zero_grad`` the zeroed gradient.  Ordered after torch's current stream
         (the backward that produced the gradients) and before what torch's current stream does next; no host sync."""
-        if self.be is None:
-            raise RuntimeError("FusedAdamW was built without a backend: it holds state but cannot step")
-        capturing = self.be._capturing
-        if not capturing:
-            self.be.wait_current()
-        self.launch(update_ema, zero_grad)
-        if not capturing:
-            self.be.release_to_current()
+        self._bracketed_launch(update_ema, zero_grad)
 
     # -- checkpoints: torch.optim.AdamW's layout
     def state_dict(self) -> dict:

@@ -33,6 +33,7 @@ from . import lib as L
 from . import optim as O
 from . import training_io as IO
 from . import unet_grad as UG
+from .backend import on_backend
 from .lr_scheduler import warmup_cosine_lr
 
 _GATES = ("processor.anat_gate", "processor.dis_gate")
@@ -248,7 +249,7 @@ class Trainer:
         ``epoch`` and ``global_step`` (optimizer steps of the run).  The device block is zeroed; means of an empty block
         are NaN."""
         be, words = self.be, self.optimizer.state.numel()
-        be.wait_current()
+        be.wait_current()                   # half a hand-off: the .cpu() below is the sync, nothing to release
         with be.ctx():
             blob = torch.cat([self.optimizer.state, self._metrics.view(torch.int32)]).cpu()     # the one sync
         self._metrics.zero_()
@@ -347,8 +348,7 @@ class Trainer:
             raise RuntimeError(f"{self.pending} micro-batch(es) are pending: flush() or optimizer_step() before the state is "
                                "taken (the accumulated gradient is not part of it)")
         device, be, sd = torch.device(device), self.be, self.module._sd
-        be.wait_current()
-        with be.ctx(), torch.no_grad():
+        with on_backend(be), be.ctx(), torch.no_grad():
             shared = {k: (self.gates[k] if k in self.gates else sd[k]).detach().to(device=device, copy=True)
                       for k in self._untrained()}
 
@@ -362,7 +362,6 @@ class Trainer:
             out = IO.pack(self.arena, self.optimizer, epoch=self.epoch, global_step=self.steps,
                           latest_update_step=self.ema_latest_step, accumulate=self.accumulate, parts=parts, device=device,
                           export=export, generators=IO.default_generators(self.device))
-        be.release_to_current()
         if device.type == "cuda":           # allocated on the backend's stream, read by the caller on torch's
             cur = torch.cuda.current_stream(self.device)
             for part in (out["state_dict"], out.get("current_model_state", {})):
@@ -383,7 +382,8 @@ class Trainer:
         state's own when it was taken before the first optimizer step)."""
         if self.pending:
             raise RuntimeError(f"{self.pending} micro-batch(es) are pending: flush() before a state is loaded")
-        self.be.release_to_current()        # the copies run on torch's stream, after what the backend still does
+        # half a hand-off: the copies run on torch's stream, after what the backend still does; the next step's bracket waits
+        self.be.release_to_current()
         info = IO.load(state, self.arena, self.optimizer, to_masters=self._to_masters, ignore=self._untrained(),
                        generators=IO.default_generators(self.device))
         with torch.no_grad():

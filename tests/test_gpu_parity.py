@@ -614,6 +614,24 @@ def test_module_cond_cache_on_device(full_sd):
         assert torch.equal(mod(x, torch.tensor(500), cA)[0], mod(x, torch.tensor([500, 500], device=DEV), cA)[0])
 
 
+@pytest.mark.parametrize("scalar", [False, True], ids=["tensor_t", "int_t"])
+def test_inner_unet_call_hands_off_both_ways(full_sd, scalar):
+    """``module.unet.unet(x, t, encoder_hidden_states=cond).sample`` (what diffusers-style callers reach) on torch's default
+    stream, reduced at once on that stream: bit for bit what ``module.unet(x, t, cond)`` gives, for a tensor timestep and
+    for a Python ``int``."""
+    mod = _module(full_sd, 128, 1)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(1, 4, 16, 16, generator=g).to(DEV)
+    cond = (torch.randn(1, 48, 768, generator=g) * 0.5).to(DEV)
+    t = 431 if scalar else torch.tensor([431], device=DEV)
+    with torch.no_grad():
+        inner = mod.unet.unet(x, t, encoder_hidden_states=cond).sample
+        total = inner.double().sum()                    # read on the current stream, no synchronisation in between
+        outer = mod.unet(x, torch.tensor([431], device=DEV), cond)
+    assert torch.equal(inner, outer)
+    assert float(total) == float(outer.double().sum()) and bool(torch.isfinite(outer).all())
+
+
 def test_main_cli_end_to_end(full_sd, tmp_path):
     """``main()`` as the reference CLI runs it (inference_pipeline_ip.py:566-669): YAML config + tensors-only
     checkpoint (tiny CLIP tower inside, geometry read from its tensors) + structure image -> PNG sequence + grid."""
