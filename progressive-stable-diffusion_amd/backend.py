@@ -876,6 +876,85 @@ class HipBackend:
                              f"got {tuple(table.shape)} {table.dtype}, n_wgs {n_wgs}")
         L.check(fn(_p(src), src.numel(), _p(table), int(n_desc), int(n_wgs), self.s))
 
+    # ------------------------------------------------------------------ evaluation metrics (csrc/metrics.hip)
+    def metrics_scratch_bytes(self, n, m=0, sigmas=0):
+        """Bytes of scratch ``feat_prepare`` / ``rbf_mmd`` take for sets of ``n`` and ``m`` rows and ``sigmas`` bandwidths."""
+        need = int(self.lib.dadd_metrics_scratch_bytes(int(n), int(m), int(sigmas)))
+        if need < 0:
+            raise ValueError(f"metrics: no scratch size for n = {n}, m = {m}, {sigmas} bandwidths")
+        return need
+
+    @staticmethod
+    def _prepared(op, what, xc, sq, d):
+        """A prepared set: fp32 contiguous [rows][ldc] with ldc >= d rounded up to ``lib.METRICS_KPAD`` and a multiple of 4,
+        and its squared norms fp32 [rows]."""
+        kp = -(-int(d) // L.METRICS_KPAD) * L.METRICS_KPAD
+        ok = xc.dtype == torch.float32 and xc.dim() == 2 and xc.is_contiguous() and xc.shape[1] >= kp and xc.shape[1] % 4 == 0 \
+            and sq.dtype == torch.float32 and sq.is_contiguous() and tuple(sq.shape) == (xc.shape[0],)
+        if not ok:
+            raise ValueError(f"{op}: {what} must be contiguous fp32 [rows][>= {kp}] with fp32 [rows] squared norms, got "
+                             f"{tuple(xc.shape)} {xc.dtype} and {tuple(sq.shape)} {sq.dtype}")
+
+    def clip_preprocess(self, frames, out, mean, std):
+        """u8 NHWC ``frames`` [B,H,W,3] -> fp32 NCHW ``out`` [B,3,S,S]: shortest-edge bicubic resize to S, centre crop, /255
+        and normalisation with ``mean`` / ``std`` (three floats each), as transformers' ``CLIPImageProcessor``."""
+        b, h, w, c = frames.shape
+        s = out.shape[-1]
+        assert c == 3 and frames.dtype == torch.uint8 and frames.is_contiguous()
+        assert out.dtype == torch.float32 and tuple(out.shape) == (b, 3, s, s) and out.is_contiguous()
+        assert len(mean) == 3 and len(std) == 3
+        L.check(self.lib.dadd_clip_preprocess_u8(_p(frames), _p(out), b, h, w, s, (L.f32 * 3)(*mean), (L.f32 * 3)(*std), self.s))
+
+    def feat_prepare(self, x, y, xc, yc, sqx, sqy, center, scratch, normalize=False):
+        """``x`` [n,D] and optionally ``y`` [m,D] (fp32 rows, unit column stride) -> the prepared sets ``xc`` / ``yc``
+        [rows][ldc], their squared norms ``sqx`` / ``sqy`` and the common ``center`` [>= D rounded up to 32]; ``normalize``
+        scales every row to unit length first.  ``scratch``: uint8, ``metrics_scratch_bytes(n, m)`` bytes."""
+        n, d = x.shape
+        assert x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) >= d
+        self._prepared("feat_prepare", "xc / sqx", xc, sqx, d)
+        assert xc.shape[0] == n and center.dtype == torch.float32 and center.is_contiguous() and center.numel() >= xc.shape[1]
+        m, ldy = 0, 0
+        if y is not None:
+            m, ldy = y.shape[0], y.stride(0)
+            assert y.dtype == torch.float32 and y.shape[1] == d and y.stride(1) == 1 and ldy >= d
+            self._prepared("feat_prepare", "yc / sqy", yc, sqy, d)
+            assert yc.shape == (m, xc.shape[1])
+        assert scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= self.metrics_scratch_bytes(n, m)
+        L.check(self.lib.dadd_feat_prepare_f32(_p(x), n, x.stride(0), _p(y), m, ldy, d, int(bool(normalize)), _p(xc), _p(yc),
+                                               xc.shape[1], _p(sqx), _p(sqy), _p(center), _p(scratch), scratch.numel(), self.s))
+
+    def rbf_mmd(self, xc, sqx, yc, sqy, d, sigmas, out, scratch):
+        """Prepared sets -> ``out`` (float64 [3 S + 1]): per bandwidth the means of u = 1 - k over the pairs of XX (i != j),
+        of YY (i != j) and of XY, as ``out[:3 S].view(3, S)``, and the unbiased MMD^2 in ``out[3 S]``."""
+        s = len(sigmas)
+        self._prepared("rbf_mmd", "xc / sqx", xc, sqx, d)
+        self._prepared("rbf_mmd", "yc / sqy", yc, sqy, d)
+        assert xc.shape[1] == yc.shape[1] and 1 <= s <= L.METRICS_MAX_SIGMAS
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 3 * s + 1
+        assert scratch.dtype == torch.uint8 and scratch.is_contiguous() \
+            and scratch.numel() >= self.metrics_scratch_bytes(xc.shape[0], yc.shape[0], s)
+        L.check(self.lib.dadd_rbf_mmd_f32(_p(xc), _p(sqx), xc.shape[0], _p(yc), _p(sqy), yc.shape[0], int(d), xc.shape[1],
+                                          (L.f32 * s)(*sigmas), s, _p(out), out.data_ptr() + 8 * 3 * s, _p(scratch),
+                                          scratch.numel(), self.s))
+
+    def knn_radius(self, xc, sqx, d, k, radius):
+        """``radius`` [n] fp32: the distance from every row of the prepared set to its k-th nearest other row (the (k+1)-th
+        smallest with itself counted), ``cdist(x, x).topk(k + 1, largest=False).values[:, -1]``."""
+        self._prepared("knn_radius", "xc / sqx", xc, sqx, d)
+        assert radius.dtype == torch.float32 and radius.is_contiguous() and tuple(radius.shape) == (xc.shape[0],)
+        L.check(self.lib.dadd_knn_radius_f32(_p(xc), _p(sqx), xc.shape[0], int(d), xc.shape[1], int(k), _p(radius), self.s))
+
+    def manifold_hits(self, qc, sqq, rc, sqr, radius, d, hit):
+        """``hit`` [nq] int32: 1 where the query row lies within ``radius[j]`` of some reference row j (both sets prepared
+        by one ``feat_prepare`` call, so centred on the same vector)."""
+        self._prepared("manifold_hits", "qc / sqq", qc, sqq, d)
+        self._prepared("manifold_hits", "rc / sqr", rc, sqr, d)
+        assert qc.shape[1] == rc.shape[1]
+        assert radius.dtype == torch.float32 and radius.is_contiguous() and tuple(radius.shape) == (rc.shape[0],)
+        assert hit.dtype == torch.int32 and hit.is_contiguous() and tuple(hit.shape) == (qc.shape[0],)
+        L.check(self.lib.dadd_manifold_hits_f32(_p(qc), _p(sqq), qc.shape[0], _p(rc), _p(sqr), _p(radius), rc.shape[0], int(d),
+                                                qc.shape[1], _p(hit), self.s))
+
     def self_attn(self, qkv, out, heads):
         """qkv [B,N,3C] (q|k|v blocks of C columns); out [B,N,C]."""
         b, n, c3 = qkv.shape

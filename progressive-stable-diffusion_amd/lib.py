@@ -15,7 +15,9 @@ CSRC = os.path.join(_HERE, "csrc")
 # sources compiled once (fp16 only, or no 16-bit kernel of their own)
 _SINGLE_SOURCES = ("attn2_fused", "ffn_block", "tf_head", "conditioning", "api",
                    # training: gradient statistics, clip / loss-scale scalars and the fused AdamW pass (the 16-bit type is a flag)
-                   "optim")
+                   "optim",
+                   # evaluation: CLIP preprocessing, feature preparation and the pair kernels of CMMD / precision / recall (fp32 only)
+                   "metrics")
 # sources compiled a second time as NAME_bf16.hip, the bf16 twin (csrc/bf16_names.h)
 _TWINNED_SOURCES = (
     # the UNet's generic-path kernels
@@ -303,6 +305,21 @@ PLAN_REFRESH_PROTOTYPES = _with_bf16({
     "dadd_plan_refresh_f16": (C.c_int, [vp, C.c_longlong, vp, C.c_int, C.c_int, vp]),
 })
 
+# include/dadd_hip_metrics.h: evaluation metrics (csrc/metrics.hip)
+METRICS_KPAD, METRICS_MAX_SIGMAS, METRICS_MAX_K = 32, 8, 7
+
+# every symbol include/dadd_hip_metrics.h declares
+METRICS_PROTOTYPES = {
+    "dadd_clip_preprocess_u8": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(f32), C.POINTER(f32), vp]),
+    "dadd_metrics_scratch_bytes": (C.c_longlong, [C.c_int] * 3),
+    "dadd_feat_prepare_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                        vp, C.c_longlong, vp]),
+    "dadd_rbf_mmd_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(f32), C.c_int, vp, vp, vp,
+                                   C.c_longlong, vp]),
+    "dadd_knn_radius_f32": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dadd_manifold_hits_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+}
+
 # The registry: header under include/ -> the table of what it declares.  A new header is one entry here; load(), the
 # dependencies of build() and the symbol check of __graft_entry__.build() follow.
 HEADER_PROTOTYPES = {
@@ -318,6 +335,7 @@ HEADER_PROTOTYPES = {
     "dadd_hip_optim.h": OPTIM_PROTOTYPES,
     "dadd_hip_relayout.h": RELAYOUT_PROTOTYPES,
     "dadd_hip_plan_refresh.h": PLAN_REFRESH_PROTOTYPES,
+    "dadd_hip_metrics.h": METRICS_PROTOTYPES,
 }
 ALL_PROTOTYPES = {}
 for _header, _table in HEADER_PROTOTYPES.items():
